@@ -21,16 +21,23 @@ Workloads (config.workload):
       GraspPredicter + NunocsPredicter per category with its own weights), --candidates-total (500,000) candidates in TOTAL cut into
       contiguous slices over the ranks (strong scaling), split-bf16 MFMA arithmetic (--precision bf16x3) unless told otherwise.
 All inputs are resident in HBM before the timed region; weights are seeded random (the reference ships no checkpoints).
-`value` is measured under --precision (default f32: exact-f32 MFMA, the reference's arithmetic); the split-precision modes of
-the product (f16x3, f16fp8x2, bf16x3; opt-in via CATGRASP_AMD_PRECISION) are measured in the same run and reported under `secondary`.
+`value` is measured under --precision (default f32: exact-f32 MFMA, the reference's arithmetic).
 
-`roofline.traffic` is MEASURED for the run at N = 1 whenever rocprofv3 is on the box (default; --no-pmc-traffic turns it off): after
-the timed region two bounded child passes of the same workload run under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate
-passes, counters only).  If a pass fails the line falls back to the labelled constant from profiles/ and says so.
-`rccl_selftest` (N = 1): after the timed region the step's records are gathered once more through a ONE-rank `nccl` process group with
-the collective forced -- the pad / all_gather_into_tensor / trim of the N-rank job on RCCL itself -- and compared with the ungathered ones.
+A plain run sets up, warms up, times --steps steps and prints the line: `value`, `ms_per_step` (wall-clock of one timed step), the
+workload's `config`, the dominant kernel's `roofline` from the HIP events of the timed steps, `records_sha256`.  --dump-outputs DIR
+writes the (p_G, code) records of the last timed step to DIR/records.npy (float32, one row per candidate in global order).
+Everything else the benchmark measures runs only with --full (each block can still be switched off by its --no-* option):
+  the split-precision modes of the product (f16x3, f16fp8x2, bf16x3; opt-in via CATGRASP_AMD_PRECISION) under `secondary`, and the
+  weak-scaling figure when N > 1; `api` (reference entry points, pick cycle) and `pp_encoder`; `projected_scaling`; `roofline_filter`;
+  `configs` (C4 and C5 at full size); `cpu_baseline`;
+  `roofline.traffic` MEASURED for the run at N = 1 whenever rocprofv3 is on the box (--no-pmc-traffic turns it off): after the timed
+  region two bounded child passes of the same workload run under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes,
+  counters only).  If a pass fails, or without --full, the line quotes the labelled constant from profiles/ and says so;
+  `rccl_selftest` (N = 1): after the timed region the step's records are gathered once more through a ONE-rank `nccl` process group
+  with the collective forced -- the pad / all_gather_into_tensor / trim of the N-rank job on RCCL itself -- and compared with the
+  ungathered ones.
 
-Launch: python bench.py --gpus 1 --steps K --warmup W
+Launch: python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
         ... bench.py --gpus 8 --workload C4 --candidates-total 200000           (C4)
         ... bench.py --gpus 8 --workload C5                                     (C5)
@@ -598,6 +605,20 @@ def claim_stdout():
         os.dup2(2, 1)
 
 
+def dump_outputs(dirname, records, limit_bytes=64 << 20):
+    """--dump-outputs: what the timed path returned in its last step -- the (p_G, reject code) record of every candidate, float32
+    (n_total, 2), global candidate order -- as DIR/records.npy.  A batch whose records exceed `limit_bytes` is written as a fixed,
+    seeded sample of rows (ascending), their candidate indices in DIR/records_rows.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    rec = records.detach().float().cpu().numpy()
+    if rec.nbytes > limit_bytes:
+        m = limit_bytes // (rec.itemsize * rec.shape[1] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(len(rec), m, replace=False))
+        rec = rec[rows]
+        np.save(os.path.join(dirname, 'records_rows.npy'), rows.astype(np.float64))
+    np.save(os.path.join(dirname, 'records.npy'), np.ascontiguousarray(rec))
+
+
 def emit(obj):
     data = (json.dumps(obj) + '\n').encode()
     if _REAL_STDOUT is None:
@@ -622,19 +643,24 @@ def main():
                     help='arithmetic of the timed path (`value`): f32 = exact-f32 MFMA (the reference\'s arithmetic); f16x3 / bf16x3 = split MFMA '
                          'products (3 MFMAs on hi+lo 16-bit pieces, f32 accumulation; logits within ~2e-6 / ~2e-5 of the float64 evaluation).  '
                          'Default f32; bf16x3 for C5 (configs[4] names the bf16 MFMA path)')
-    ap.add_argument('--secondary', default='f16x3,bf16x3,f16fp8x2', help='comma list of further precisions measured in the same run ("" = none)')
+    ap.add_argument('--secondary', default='f16x3,bf16x3,f16fp8x2', help='--full: comma list of further precisions measured in the same run ("" = none)')
     ap.add_argument('--chunk', type=int, default=None,
                     help='candidates per network launch (default: GraspPredicter\'s 16,384 = 805 MB of materialised input per chunk)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-api', action='store_true', help='skip the reference-API wall-clock block')
     ap.add_argument('--pmc-traffic', dest='pmc_traffic', action='store_true', default=None,
-                    help='measure roofline.traffic for this run with two rocprofv3 --pmc child passes (N = 1 only; adds ~1 min).  Default: on '
-                         'when rocprofv3 is present')
+                    help='--full: measure roofline.traffic for this run with two rocprofv3 --pmc child passes (N = 1 only; adds ~1 min).  '
+                         'Default: on when rocprofv3 is present')
     ap.add_argument('--no-pmc-traffic', dest='pmc_traffic', action='store_false', help='quote the constant from profiles/ instead')
     ap.add_argument('--pmc-traffic-all', action='store_true', help='measure the traffic of every secondary precision too (two child passes each)')
     ap.add_argument('--no-projection', action='store_true', help='skip the projected_scaling block (N = 1: slice timings of the 2 / 4 / 8-rank shards)')
     ap.add_argument('--no-configs', action='store_true', help='skip the `configs` block of the default line (C4 and C5 at full size, 2 warm-ups + 3 steps each)')
     ap.add_argument('--no-rccl-selftest', action='store_true', help='skip the one-rank RCCL all-gather check after the timed region (N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every block beyond the headline figure (secondary precisions, weak scaling, api, pick cycle, encoder table, '
+                         'projected scaling, RCCL self-test, counter passes, filter roofline, C4 / C5 configs, CPU baseline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the (p_G, code) records of the last timed step to DIR/records.npy (float32)')
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)      # the child run of --pmc-traffic: workload only
     ap.add_argument('--pmc-filter-child', action='store_true', help=argparse.SUPPRESS)   # the child run of pmc_filter_issue: object 0's filter calls
     args = ap.parse_args()
@@ -841,23 +867,27 @@ def main():
     prim = measure(args.precision)
     ref_out = prim['out'].clone()
     lap('primary measurement (warm-up + timed steps)')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ref_out)
+        lap('--dump-outputs')
     # the reference-API wall-clock right behind the primary measurement (same clock / thermal state as `value`), before the minutes of
     # split-precision runs below
-    api = api_block(batch, gp, device) if (rank == 0 and world == 1 and not args.no_api) else None
+    api = api_block(batch, gp, device) if (args.full and rank == 0 and world == 1 and not args.no_api) else None
     if api is not None:
         try:
             api['pick_cycle'] = pick_cycle_block(batch, gp, npreds[cats[0]], device)
         except Exception as e:          # an extra: never let it take the bench line down
             api['pick_cycle'] = {'error': f'{type(e).__name__}: {e}'[:300]}
-    lap('api block (reference entry points, pick cycle)')
+    if args.full:
+        lap('api block (reference entry points, pick cycle)')
     secondary = []
-    for other in [p for p in args.secondary.split(',') if p and p != args.precision]:
+    for other in [p for p in args.secondary.split(',') if args.full and p and p != args.precision]:
         r = measure(other)
         secondary.append({'precision': other, 'dtype': DTYPE[other], 'value': round(n_total * args.steps / r['dt'], 1),
                           'ms_per_step': round(r['dt'] / args.steps * 1e3, 3), 'roofline': roofline(other, r),
                           'max_abs_p_G_difference_vs_primary': float((r['out'][:, 0] - ref_out[:, 0]).abs().max().item()),
                           'codes_identical_to_primary': bool(torch.equal(r['out'][:, 1], ref_out[:, 1]))})
-    if world > 1 and args.workload == 'C3' and args.scaling == 'strong':
+    if args.full and world > 1 and args.workload == 'C3' and args.scaling == 'strong':
         # the weak-scaling figure of the same scene next to the strong one: every rank scores its own --candidates (different seeds)
         ww = build_workload('C3', 'weak')
         wbatch, wn = ww['batch'], ww['n_total']
@@ -868,17 +898,19 @@ def main():
                           'note': 'per-GPU work fixed: N x the single-GPU batch, gathered by the same one all_gather'})
         del wbatch, ww, r
     engine.set_precision(args.precision)
-    lap('secondary precisions')
+    if args.full:
+        lap('secondary precisions')
 
     projected = None
-    if world == 1 and rank == 0 and args.scaling == 'strong' and not args.no_projection:
+    if args.full and world == 1 and rank == 0 and args.scaling == 'strong' and not args.no_projection:
         projected = projected_scaling_block(batch, n_total, prim['dt'] / args.steps)
     selftest = None
-    if world == 1 and not args.no_rccl_selftest and backend == 'nccl':
+    if args.full and world == 1 and not args.no_rccl_selftest and backend == 'nccl':
         selftest = rccl_selftest(batch, n_total, ref_out, device)
-    lap('projected scaling + rccl self-test')
+    if args.full:
+        lap('projected scaling + rccl self-test')
 
-    if rank == 0 and world == 1 and args.pmc_traffic:
+    if args.full and rank == 0 and world == 1 and args.pmc_traffic:
         # the primary arithmetic and, when it is among the secondaries, bf16x3 (the C5 arithmetic); --pmc-traffic-all: every secondary
         wanted = [args.precision] + [x['precision'] for x in secondary if 'precision' in x and 'roofline' in x
                                      and (args.pmc_traffic_all or x['precision'] == 'bf16x3')]
@@ -893,7 +925,8 @@ def main():
                 per, source = measured_traffic[x['precision']]
                 x['roofline']['traffic'] = int(per * x['roofline']['candidates_per_launch'])
                 x['roofline']['traffic_source'] = source
-    lap('traffic counter passes (rocprofv3 --pmc children)')
+    if args.full:
+        lap('traffic counter passes (rocprofv3 --pmc children)')
     METRIC = {'C3': 'grasp candidates scored+collision-checked /sec, 20k-pt clutter scene',
               'C4': 'grasp candidates scored+collision-checked /sec, 40k-pt scene, candidates sharded over the GPUs',
               'C5': 'grasp candidates scored+collision-checked /sec, 60k-pt mixed-category bin, candidates sharded over the GPUs'}
@@ -979,7 +1012,7 @@ def main():
             line['rccl_selftest'] = selftest
         if 'bgi' in prim:
             line['roofline_hbm'] = prim['bgi']
-        if world == 1:
+        if args.full and world == 1:
             try:
                 line['roofline_filter'] = filter_roofline_block(batch, device, issue=pmc_filter_issue(args) if args.pmc_traffic else (None, '--no-pmc-traffic'))
             except Exception as e:          # an extra: never let it take the bench line down
@@ -992,8 +1025,9 @@ def main():
                 line['pp_encoder'] = encoder_block(batch, device)
             except Exception as e:          # an extra: never let it take the bench line down
                 line['pp_encoder'] = {'error': f'{type(e).__name__}: {e}'[:300]}
-        lap('filter roofline, encoder block')
-        if world == 1 and args.workload == 'C3' and args.scaling == 'strong' and not args.no_configs:
+        if args.full:
+            lap('filter roofline, encoder block')
+        if args.full and world == 1 and args.workload == 'C3' and args.scaling == 'strong' and not args.no_configs:
             # the other two GPU configurations of BASELINE.json in the same driver-run line
             line['configs'] = {}
             for wl_name, prec, pmc_total in (('C4', 'f32', 50000), ('C5', 'bf16x3', 150000)):
@@ -1003,7 +1037,7 @@ def main():
                     line['configs'][wl_name] = {'error': f'{type(e).__name__}: {e}'[:300]}
                 torch.cuda.empty_cache()
                 lap(f'configs.{wl_name}')
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(batch, sd_cls, sd_seg)
             lap('cpu baseline')
         line['timing_s'] = dict(timing, total=round(sum(timing.values()), 2))

@@ -23,11 +23,11 @@ case $JOB in
     stats pp_encoder_msg python scripts/pp_encoder_profile.py --trace --msg
     head -12 $O/pp_encoder_kernel_stats.csv | cut -c1-160 ;;
   bench)      # the default bench line + its kernel statistics
-    ( time timeout 900 python bench.py "$@" ) > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; head -c 600 $O/bench.json
+    ( time timeout 900 python bench.py --full "$@" ) > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; head -c 600 $O/bench.json
     stats bench python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-api --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs ;;
   pick)       # the pick cycle block of the bench alone (api.pick_cycle) + the tests of the pipeline
     timeout 600 python -m pytest tests/test_pipeline_gpu.py tests/test_collision_gpu.py tests/test_dataparallel_gpu.py tests/test_pointnet2_encoder_gpu.py -m gpu -x -q > $O/pytest.log 2>&1; tail -8 $O/pytest.log
-    timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+    timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
     python -c "import json;d=json.load(open('$O/bench.json'));print(json.dumps(d['api']['pick_cycle'],indent=1))" | head -80 ;;
   small)      # small-call latency with / without the channel split + the tests that pin its bits + the multi-rank dev runs
     timeout 900 python -m pytest tests/test_pointnet_gpu.py tests/test_pointnet_blocks_gpu.py tests/test_predicter_gpu.py -m gpu -x -q > $O/pytest.log 2>&1; tail -5 $O/pytest.log
@@ -57,11 +57,11 @@ case $JOB in
     ( time timeout 900 python bench.py ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 300 $O/bench.err; head -c 500 $O/bench_default_flags.json ;;
   r6a)        # round 6, first contact: stricter encoder tests, refactored bench (multirank + the default line with `configs`)
     timeout 1200 python -m pytest tests/test_pointnet2_encoder_gpu.py tests/test_primitives_gpu.py tests/test_bench_multirank_gpu.py -m gpu -q > $O/pytest.log 2>&1; tail -25 $O/pytest.log
-    ( time timeout 900 python bench.py ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 600 $O/bench.err
+    ( time timeout 900 python bench.py --full ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 600 $O/bench.err
     python -c "import json;d=json.load(open('$O/bench_default_flags.json'));print(json.dumps(d['timing_s'],indent=1));print(json.dumps({k:{kk:v.get(kk) for kk in ("value","ms_per_step","wall_s","error")} for k,v in d['configs'].items()}));print(d['value'],d['ms_per_step'])" ;;
   r6b)        # round 6: the one-launch filter (FilterPlan) -- parity tests, the step, the default line
     timeout 1500 python -m pytest tests/test_collision_gpu.py tests/test_workload_gpu.py tests/test_pipeline_gpu.py tests/test_fullsize_properties_gpu.py tests/test_bench_multirank_gpu.py -m gpu -q -x > $O/pytest.log 2>&1; tail -15 $O/pytest.log
-    ( time timeout 900 python bench.py ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 400 $O/bench.err
+    ( time timeout 900 python bench.py --full ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 400 $O/bench.err
     python -c "import json;d=json.load(open('$O/bench_default_flags.json'));print(json.dumps(d['timing_s'],indent=1));print(json.dumps({k:{kk:v.get(kk) for kk in ('value','ms_per_step','wall_s','error')} for k,v in d['configs'].items()}));print(d['value'],d['ms_per_step']);print(json.dumps({k:v for k,v in d['roofline_filter'].items() if k not in ('note','cache_level')}));print(json.dumps(d['api']['pick_cycle']['default']))" ;;
   pmcsplit)   # issue-side counters of the split-precision encoder-pass kernels (C5's dominant kernel: <2, 8, false, false> = bf16x3), 4,096 candidates
     C1="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"
@@ -105,13 +105,13 @@ case $JOB in
     CATGRASP_AMD_GEMM_CHAIN=0 timeout 300 python scripts/time_predict_small.py > $O/predict_small_nochain.txt 2>&1; echo --- no chain; grep candidates $O/predict_small_nochain.txt | head -4
     CATGRASP_AMD_GEMM_CHAIN=1 timeout 300 python scripts/pp_encoder_profile.py $O/pp_encoder_chain.json > $O/pp_encoder_chain.txt 2>&1; grep -o '"clouds": [0-9]*\|"encoder_ms": [0-9.]*\|gemm_chain": [0-9.]*' $O/pp_encoder_chain.txt | head -12
     CATGRASP_AMD_GEMM_CHAIN=0 timeout 300 python scripts/pp_encoder_profile.py $O/pp_encoder_nochain.json > $O/pp_encoder_nochain.txt 2>&1; grep -o '"clouds": [0-9]*\|"encoder_ms": [0-9.]*\|gemm_chain": [0-9.]*' $O/pp_encoder_nochain.txt | head -12
-    timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+    timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
     python -c "import json;d=json.load(open('$O/bench.json'));p=d['api']['pick_cycle'];print(json.dumps({k:(v['wall_ms_per_object'] if isinstance(v,dict) and 'wall_ms_per_object' in v else v) for k,v in p.items() if k!='note'},indent=1)[:1500]);print(json.dumps(p['default']['ms_per_object_by_stage']))" ;;
   r6e)        # filter workgroups-per-CU knob, overlapped pick cycle with wait instrumentation
     for cap in 16 32 64 4096; do echo cap $cap; CATGRASP_AMD_FILTER_BLOCKS_PER_CU=$cap timeout 300 python scripts/time_filter_plan.py > $O/time_cap$cap.txt 2>&1; tail -1 $O/time_cap$cap.txt | cut -c1-200; done
     CATGRASP_AMD_FILTER_BLOCKS_PER_CU=4096 timeout 300 python scripts/time_filter_plan.py 400000 > $O/time_cap4096_400k.txt 2>&1; tail -1 $O/time_cap4096_400k.txt | cut -c1-200
     timeout 1500 python -m pytest tests/test_pipeline_gpu.py tests/test_collision_gpu.py tests/test_pointnet_gpu.py tests/test_pointnet2_encoder_gpu.py -m gpu -q -x > $O/pytest.log 2>&1; tail -4 $O/pytest.log
-    timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+    timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
     python -c "import json;d=json.load(open('$O/bench.json'));p=d['api']['pick_cycle'];print(json.dumps({k:(v['wall_ms_per_object'] if isinstance(v,dict) and 'wall_ms_per_object' in v else v) for k,v in p.items() if k!='note'},indent=1)[:1500]);print(json.dumps(p['default']['ms_per_object_by_stage']))" ;;
   r6f)        # split kernel without SLP-packed f32 ops; stages-thread instrumentation; filter cap at 400k
     for i in 1 2 3; do
@@ -121,21 +121,21 @@ case $JOB in
     timeout 300 python scripts/time_filter_plan.py 400000 > $O/time_cap32_400k.txt 2>&1; tail -1 $O/time_cap32_400k.txt | cut -c1-200
     CATGRASP_AMD_FILTER_BLOCKS_PER_CU=16 timeout 300 python scripts/time_filter_plan.py 400000 > $O/time_cap16_400k.txt 2>&1; tail -1 $O/time_cap16_400k.txt | cut -c1-200
     timeout 300 python scripts/time_filter_plan.py > $O/time_cap32.txt 2>&1; tail -1 $O/time_cap32.txt | cut -c1-200
-    timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+    timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs --secondary "" > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
     python -c "import json;d=json.load(open('$O/bench.json'));p=d['api']['pick_cycle'];print(json.dumps({k:(v['wall_ms_per_object'] if isinstance(v,dict) and 'wall_ms_per_object' in v else v) for k,v in p.items() if k!='note'},indent=1)[:1500]);print(json.dumps(p['default']['ms_per_object_by_stage']))" ;;
   r6lines)    # the round's bench lines: default flags (C3 + configs), C4 and C5 alone, kernel statistics of the default step
-    ( time timeout 900 python bench.py ) > $O/bench_line.json 2> $O/bench.err; tail -c 200 $O/bench.err
-    timeout 900 python bench.py --workload C4 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c4_n1.json 2> $O/c4.err; head -c 300 $O/bench_line_c4_n1.json; echo
-    timeout 900 python bench.py --workload C5 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c5_n1.json 2> $O/c5.err; head -c 300 $O/bench_line_c5_n1.json; echo
+    ( time timeout 900 python bench.py --full ) > $O/bench_line.json 2> $O/bench.err; tail -c 200 $O/bench.err
+    timeout 900 python bench.py --full --workload C4 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c4_n1.json 2> $O/c4.err; head -c 300 $O/bench_line_c4_n1.json; echo
+    timeout 900 python bench.py --full --workload C5 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c5_n1.json 2> $O/c5.err; head -c 300 $O/bench_line_c5_n1.json; echo
     stats bench python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-api --no-pmc-traffic --no-rccl-selftest --no-projection --no-configs
     stats bench_c5 python bench.py --workload C5 --steps 3 --warmup 1 --no-cpu-baseline --no-api --no-pmc-traffic --no-rccl-selftest --no-projection --secondary ""
     python -c "import json;d=json.load(open('$O/bench_line.json'));print(json.dumps(d['timing_s']));print(d['value'],d['ms_per_step'],{k:(v.get('value'),v.get('ms_per_step'),v.get('wall_s')) for k,v in d['configs'].items()});print(d['api']['predict_batch_small_calls']);print(d['api']['pick_cycle']['default']['wall_ms_per_object'])" ;;
   r6final)    # the driver's round-end sequence on the final tree (suite, smoke, default bench) + the C4 / C5 lines and the example in the same (warm) state
     timeout 2400 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -3 $O/pytest.log
     timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-    ( time timeout 900 python bench.py ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 200 $O/bench.err
-    timeout 900 python bench.py --workload C4 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c4_n1.json 2> $O/c4.err
-    timeout 900 python bench.py --workload C5 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c5_n1.json 2> $O/c5.err
+    ( time timeout 900 python bench.py --full ) > $O/bench_default_flags.json 2> $O/bench.err; tail -c 200 $O/bench.err
+    timeout 900 python bench.py --full --workload C4 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c4_n1.json 2> $O/c4.err
+    timeout 900 python bench.py --full --workload C5 --no-api --no-cpu-baseline --no-rccl-selftest --secondary "" > $O/bench_line_c5_n1.json 2> $O/c5.err
     timeout 300 python examples/run_scene.py > $O/example.txt 2>&1; tail -3 $O/example.txt
     python -c "import json;d=json.load(open('$O/bench_default_flags.json'));c4=json.load(open('$O/bench_line_c4_n1.json'));c5=json.load(open('$O/bench_line_c5_n1.json'));print(d['value'],d['ms_per_step'],{k:v['value'] for k,v in d['configs'].items()},'standalone',c4['value'],c5['value'],d['api']['pick_cycle']['default']['wall_ms_per_object'],d['api']['predict_batch_small_calls'][:1],d['roofline_filter']['frac'],d['timing_s']['total'])" ;;
   py)         # any script:  py scripts/x.py args...

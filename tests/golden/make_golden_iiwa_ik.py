@@ -2,7 +2,7 @@
 the vendored IKFast file compiled where it lies (oracle/build_ref.py -> oracle/_ref/libikfast_ref.so) and driven exactly like
 get_ik_within_limits (my_cpp/common.cpp:9-72).  Run in the build container (needs /root/reference):
 
-    python tests/golden/make_golden_iiwa_ik.py        ->  tests/golden/iiwa_ik_golden.npz
+    python tests/golden/make_golden_iiwa_ik.py        ->  tests/golden/iiwa_ik_golden.npz, tests/golden/iiwa_ik_golden_sols.npz
 """
 import ctypes
 import os
@@ -47,5 +47,6 @@ for i in range(N):
     nsol[i] = n
     sols[i, :min(n, 8)] = buf[:min(n, 8)]
 out = os.path.join(ROOT, 'tests', 'golden', 'iiwa_ik_golden.npz')
-np.savez_compressed(out, fk_joints=fk_joints, fk_poses=fk_poses, poses32=poses32, upper=UP, lower=LO, within=within, nsol=nsol, sols=sols)
+np.savez_compressed(out, fk_joints=fk_joints, fk_poses=fk_poses, poses32=poses32, upper=UP, lower=LO, within=within, nsol=nsol)
+np.savez_compressed(out.replace('.npz', '_sols.npz'), sols=sols)            # a file of its own: each fixture stays under 1 MiB
 print('wrote', out, os.path.getsize(out), 'bytes; within limits:', int(within.sum()), 'of', N, '; solution counts', np.unique(nsol, return_counts=True))

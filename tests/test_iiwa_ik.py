@@ -7,7 +7,9 @@ import pytest
 
 from oracle import iiwa_ik_ref as K
 
-GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'iiwa_ik_golden.npz'))
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+GOLD = dict(np.load(os.path.join(_GOLDEN, 'iiwa_ik_golden.npz')))
+GOLD['sols'] = np.load(os.path.join(_GOLDEN, 'iiwa_ik_golden_sols.npz'))['sols']       # own file: keeps each fixture under 1 MiB
 
 
 def _angdiff(a, b):

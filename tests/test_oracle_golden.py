@@ -178,3 +178,54 @@ def test_dropin_building_blocks_with_every_constructor_setting_match_the_referen
             got = sample(t.detach()).numpy()
             assert got.shape == ref.shape, (tag, i)
             assert np.abs(got - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max()), (tag, i)
+
+
+LIVE_GOLD = os.path.join(os.path.dirname(GOLD), 'reference_live_golden.npz')
+
+
+def _sample(t):
+    """The sample tests/golden/make_golden_reference_live.py records: <= 128 evenly strided elements."""
+    return t.detach().flatten()[::max(1, -(-t.numel() // 128))].numpy()
+
+
+def _close(got, ref, tol):
+    assert got.shape == ref.shape and np.abs(got - ref).max(initial=0.0) <= tol * max(1.0, np.abs(ref).max(initial=0.0))
+
+
+def test_models_match_the_recorded_reference_outputs():
+    """test_live_against_imported_reference without the reference checkout: the reference's own outputs and state_dict layout, recorded
+    by tests/golden/make_golden_reference_live.py (tests/golden/reference_live_golden.npz)."""
+    from catgrasp_amd import pointnet2 as ours
+    g = np.load(LIVE_GOLD)
+    x = torch.from_numpy(np.random.default_rng(5).normal(0, 0.5, (2, 200, 6)).astype(np.float32))
+    for kind, n_out, name in (('cls', 10, 'PointNetCls'), ('seg', 300, 'PointNetSeg')):
+        sd = synth.make_state_dict(kind, 6, n_out, seed=31)
+        y2, tf2 = (oref.pointnet_cls_forward if kind == 'cls' else oref.pointnet_seg_forward)(sd, x)
+        _close(y2.numpy() if kind == 'cls' else y2.numpy()[:, ::3, ::4], g[f'live_{kind}_y'], 2e-5)
+        assert np.abs(tf2.numpy() - g[f'live_{kind}_tf']).max() <= 2e-5
+        sa = getattr(ours, name)(6, n_out).state_dict()
+        assert list(sa.keys()) == list(g[f'live_{kind}_keys'])
+        assert [','.join(map(str, v.shape)) for v in sa.values()] == list(g[f'live_{kind}_shapes'])
+
+
+def test_training_mode_matches_the_recorded_reference():
+    """test_training_mode_equals_the_imported_reference_bit_for_bit without the reference checkout: the drop-in's train-mode forward,
+    the gradients of every parameter and the state after the step against the reference's recorded numbers (strided samples)."""
+    from catgrasp_amd import pointnet2 as ours
+    g = np.load(LIVE_GOLD)
+    x = torch.from_numpy(np.random.default_rng(8).normal(0, 0.5, (4, 120, 6)).astype(np.float32))
+    for kind, n_out, name in (('cls', 10, 'PointNetCls'), ('seg', 30, 'PointNetSeg')):
+        a = getattr(ours, name)(6, n_out)
+        a.load_state_dict(synth.make_state_dict(kind, 6, n_out, seed=3))
+        a.train()
+        torch.manual_seed(0); y, tf = a(x.clone())
+        _close(y.detach().numpy(), g[f'train_{kind}_y'], 1e-5)
+        _close(tf.detach().numpy(), g[f'train_{kind}_tf'], 1e-5)
+        y.square().sum().backward()
+        params, state = list(a.named_parameters()), list(a.state_dict().values())
+        assert sum(k.startswith(f'train_{kind}_grad_') for k in g.files) == len(params)
+        assert sum(k.startswith(f'train_{kind}_state_') for k in g.files) == len(state)
+        for i, (_, p) in enumerate(params):
+            _close(_sample(p.grad), g[f'train_{kind}_grad_{i}'], 1e-4)
+        for i, v in enumerate(state):
+            _close(_sample(v).astype(np.float64), g[f'train_{kind}_state_{i}'].astype(np.float64), 1e-5)
