@@ -12,37 +12,25 @@
 #include <stddef.h>
 #include <stdlib.h>
 #include "cg_common.hpp"
+#include "filter_compose.hpp"
 #include "../../include/catgrasp_amd.h"
 
 namespace {
+
+using cg_filter::Mat4;
+using cg_filter::mat4_mul;
+using cg_filter::normalize_col;
+using cg_filter::ComposeMultiArgs;
+using cg_filter::MultiIkArgs;
 
 constexpr int TRI_CHUNK = 128;             // posed triangles staged per wave in LDS
 constexpr int TRI_FLOATS = 15;             // 9 vertex floats + 6 AABB floats
 constexpr int WAVES = 4;
 
-struct Mat4 { float m[16]; };
-
-__device__ __forceinline__ void mat4_mul(const float* A, const float* B, float* C) {
-  float t[16];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      t[r * 4 + c] = ((A[r * 4 + 0] * B[0 * 4 + c] + A[r * 4 + 1] * B[1 * 4 + c]) + A[r * 4 + 2] * B[2 * 4 + c]) + A[r * 4 + 3] * B[3 * 4 + c];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) C[i] = t[i];
-}
-
 // A value every lane of the wave holds identically, moved to a scalar register.  The 4x4 matrices of an evaluation are wave-uniform
 // but computed by the vector ALU (gfx950 has no scalar float unit): left in VGPRs they cost ~100 registers per lane across the
 // collision loops; as SGPRs they are free operands of the lanes' v_fma.
 __device__ __forceinline__ float uni(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
-
-__device__ __forceinline__ void normalize_col(float* M, int col) {
-  const float x = M[0 * 4 + col], y = M[1 * 4 + col], z = M[2 * 4 + col];
-  const float s = (x * x + y * y) + z * z;
-  if (s > 0.0f) { const float n = sqrtf(s); M[0 * 4 + col] = x / n; M[1 * 4 + col] = y / n; M[2 * 4 + col] = z / n; }
-}
 
 // Exact float32 triangle / axis-aligned cube overlap (separating axes: 9 edge crosses, 3 box axes, plane), BRANCH-FREE: every axis
 // is evaluated and the "separated" bits are OR-ed.  In a wavefront the lanes test different (voxel, triangle) pairs, so an early
@@ -448,15 +436,9 @@ __global__ __launch_bounds__(256) void compose_grasp_pose_kernel(ComposeArgs a) 
   a.nudge[e] = (signed char)-1;
 }
 
-// The same for the evaluations of SEVERAL filterGraspPose calls at once (cg_filter_grasp_pose_multi): evaluation e belongs to the segment
-// whose [first, first + n_pose * n_sym) holds it (binary search in the device table), inside it e - first = i * n_sym + j.
-struct ComposeMultiArgs {
-  const cg_filter_segment* segs; int n_segs; long E;
-  int filter_dir;
-  const unsigned char* ik_ok;
-  signed char* codes; float* poses_out; signed char* nudge;
-};
-
+// The same for the evaluations of SEVERAL filterGraspPose calls at once (ComposeMultiArgs, filter_compose.hpp).  (cg_filter::compose_multi
+// written out rather than called: the call form is allocated differently -- 76 instead of 94 VGPRs -- and this kernel, the filter
+// without an IK stage, stays the code it was.  With the IK stage: compose_grasp_pose_multi_ik_kernel, iiwa_ik.hip.)
 __global__ __launch_bounds__(256) void compose_grasp_pose_multi_kernel(ComposeMultiArgs a) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.E) return;
@@ -818,13 +800,29 @@ extern "C" long cg_filter_segments_prepare(cg_filter_segment* h_segments, int n_
   return E;
 }
 
-extern "C" int cg_filter_grasp_pose_multi(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
-                                          const float* h_gripper_in_grasp, int filter_approach_dir_face_camera, const unsigned char* ik_ok,
-                                          const float* gripper_vertices, const int* gripper_faces, int n_gripper_faces,
-                                          const float* enclosed_vertices, const int* enclosed_faces, int n_enclosed_faces,
-                                          float resolution, signed char* codes, float* poses_out, signed char* nudge,
-                                          const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, int keep_rejected_pose,
-                                          unsigned long long* work_stats, void* stream) {
+namespace {
+
+// the number of evaluations of a PREPARED table (firsts consecutive from 0, as cg_filter_segments_prepare wrote them), or CG_ERR_ARG
+long prepared_table_size(const cg_filter_segment* h_segments, int n_segments, bool* any_open, bool* any_bg) {
+  long E = 0;
+  for (int s = 0; s < n_segments; ++s) {
+    const cg_filter_segment& g = h_segments[s];
+    if (g.n_pose < 0 || g.n_sym < 0 || (long)g.first != E) return CG_ERR_ARG;
+    E += (long)g.n_pose * g.n_sym;
+    *any_open |= g.n_open_keys > 0; *any_bg |= g.n_bg_keys > 0;
+  }
+  if (E >= (1L << 31) - 64 * 1024) return CG_ERR_ARG;
+  return E;
+}
+
+// cg_filter_grasp_pose_multi (h_ik NULL: ik_ok, if any, is the IK verdict) and cg_filter_grasp_pose_multi_ik (the fused compose + IK stage)
+int filter_multi(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
+                 const float* h_gripper_in_grasp, int filter_approach_dir_face_camera, const unsigned char* ik_ok, const cg_iiwa_ik_params* h_ik,
+                 const float* gripper_vertices, const int* gripper_faces, int n_gripper_faces,
+                 const float* enclosed_vertices, const int* enclosed_faces, int n_enclosed_faces,
+                 float resolution, signed char* codes, float* poses_out, signed char* nudge,
+                 const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, int keep_rejected_pose,
+                 unsigned long long* work_stats, void* stream) {
   if (n_segments < 0) return CG_ERR_ARG;
   if (n_segments == 0) return CG_OK;
   if (!h_segments || !d_segments || !h_gripper_in_grasp || !codes || !poses_out || !nudge) return CG_ERR_ARG;
@@ -832,20 +830,22 @@ extern "C" int cg_filter_grasp_pose_multi(const cg_filter_segment* h_segments, c
   if ((n_gripper_faces > 0 && (!gripper_vertices || !gripper_faces)) || (n_enclosed_faces > 0 && (!enclosed_vertices || !enclosed_faces)))
     return CG_ERR_ARG;
   if (((uintptr_t)poses_out & 15) != 0) return CG_ERR_ARG;
-  // the table must be a prepared one: firsts consecutive from 0 (cg_filter_segments_prepare wrote them)
-  long E = 0;
   bool any_open = false, any_bg = false;
-  for (int s = 0; s < n_segments; ++s) {
-    const cg_filter_segment& g = h_segments[s];
-    if (g.n_pose < 0 || g.n_sym < 0 || (long)g.first != E) return CG_ERR_ARG;
-    E += (long)g.n_pose * g.n_sym;
-    any_open |= g.n_open_keys > 0; any_bg |= g.n_bg_keys > 0;
-  }
+  const long E = prepared_table_size(h_segments, n_segments, &any_open, &any_bg);
+  if (E < 0) return CG_ERR_ARG;
   if (E == 0) return CG_OK;
-  if (E >= (1L << 31) - 64 * 1024) return CG_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   ComposeMultiArgs c{d_segments, n_segments, E, filter_approach_dir_face_camera, ik_ok, codes, poses_out, nudge};
-  hipLaunchKernelGGL(compose_grasp_pose_multi_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, c);
+  if (h_ik) {
+    MultiIkArgs k;
+    k.cam_in_world = load_mat(h_ik->cam_in_world); k.ee_in_grasp = load_mat(h_ik->ee_in_grasp);
+    for (int j = 0; j < 7; ++j) { k.lim.up[j] = h_ik->upper[j]; k.lim.lo[j] = h_ik->lower[j]; }
+    k.ee_out = nullptr;
+    const int status = cg_filter::launch_compose_multi_ik(c, k, false, st);
+    if (status != CG_OK) return status;
+  } else {
+    hipLaunchKernelGGL(compose_grasp_pose_multi_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, c);
+  }
   FilterArgs a;
   a.E = E;
   a.gripper_in_grasp = load_mat(h_gripper_in_grasp);
@@ -868,6 +868,52 @@ extern "C" int cg_filter_grasp_pose_multi(const cg_filter_segment* h_segments, c
   }
   hipLaunchKernelGGL((filter_grasp_pose_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
   return cg_hip_status(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int cg_filter_grasp_pose_multi(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
+                                          const float* h_gripper_in_grasp, int filter_approach_dir_face_camera, const unsigned char* ik_ok,
+                                          const float* gripper_vertices, const int* gripper_faces, int n_gripper_faces,
+                                          const float* enclosed_vertices, const int* enclosed_faces, int n_enclosed_faces,
+                                          float resolution, signed char* codes, float* poses_out, signed char* nudge,
+                                          const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, int keep_rejected_pose,
+                                          unsigned long long* work_stats, void* stream) {
+  return filter_multi(h_segments, d_segments, n_segments, h_gripper_in_grasp, filter_approach_dir_face_camera, ik_ok, nullptr,
+                      gripper_vertices, gripper_faces, n_gripper_faces, enclosed_vertices, enclosed_faces, n_enclosed_faces, resolution,
+                      codes, poses_out, nudge, h_open_grid, h_enc_grid, keep_rejected_pose, work_stats, stream);
+}
+
+extern "C" int cg_filter_grasp_pose_multi_ik(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
+                                             const float* h_gripper_in_grasp, int filter_approach_dir_face_camera, const cg_iiwa_ik_params* h_ik,
+                                             const float* gripper_vertices, const int* gripper_faces, int n_gripper_faces,
+                                             const float* enclosed_vertices, const int* enclosed_faces, int n_enclosed_faces,
+                                             float resolution, signed char* codes, float* poses_out, signed char* nudge,
+                                             const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, int keep_rejected_pose,
+                                             unsigned long long* work_stats, void* stream) {
+  if (!h_ik) return CG_ERR_ARG;
+  return filter_multi(h_segments, d_segments, n_segments, h_gripper_in_grasp, filter_approach_dir_face_camera, nullptr, h_ik,
+                      gripper_vertices, gripper_faces, n_gripper_faces, enclosed_vertices, enclosed_faces, n_enclosed_faces, resolution,
+                      codes, poses_out, nudge, h_open_grid, h_enc_grid, keep_rejected_pose, work_stats, stream);
+}
+
+extern "C" int cg_filter_segments_ee_in_base(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
+                                             int filter_approach_dir_face_camera, const float* h_cam_in_world, const float* h_ee_in_grasp,
+                                             float* ee_out, signed char* codes, void* stream) {
+  if (n_segments < 0) return CG_ERR_ARG;
+  if (n_segments == 0) return CG_OK;
+  if (!h_segments || !d_segments || !h_cam_in_world || !h_ee_in_grasp || !ee_out || !codes) return CG_ERR_ARG;
+  if (((uintptr_t)ee_out & 15) != 0) return CG_ERR_ARG;
+  bool any_open = false, any_bg = false;
+  const long E = prepared_table_size(h_segments, n_segments, &any_open, &any_bg);
+  if (E < 0) return CG_ERR_ARG;
+  if (E == 0) return CG_OK;
+  ComposeMultiArgs c{d_segments, n_segments, E, filter_approach_dir_face_camera, nullptr, codes, nullptr, nullptr};
+  MultiIkArgs k;
+  k.cam_in_world = load_mat(h_cam_in_world); k.ee_in_grasp = load_mat(h_ee_in_grasp);
+  for (int j = 0; j < 7; ++j) { k.lim.up[j] = 0.0; k.lim.lo[j] = 0.0; }
+  k.ee_out = ee_out;
+  return cg_filter::launch_compose_multi_ik(c, k, true, (hipStream_t)stream);
 }
 
 extern "C" int cg_mesh_voxels_collide(const float* vertices, const int* faces, int n_faces, const float* poses, long n_poses,

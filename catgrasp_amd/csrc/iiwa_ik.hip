@@ -1,95 +1,65 @@
-// get_ik_within_limits (my_cpp/common.cpp:9-72) on the device: closed-form IK of the KUKA LBR iiwa14 with the redundancy
-// joint (index 2) fixed at 0, one thread per end-effector pose, float64.  The algorithm, its derivation from the arm's DH
-// table and the degeneracy windows of the reference's generated solver that it reproduces are stated in
-// oracle/iiwa_ik_ref.py (the host restatement of the same arithmetic used by the tests, itself pinned to the real solver's
-// answers in tests/golden/iiwa_ik_golden.npz).
+// get_ik_within_limits (my_cpp/common.cpp:9-72) on the device, one thread per end-effector pose: the closed-form iiwa14 IK of
+// iiwa_ik.hpp over a stored (E,16) ee_in_base array, and fused into the pose composition of the multi-segment filter.
 #include "cg_common.hpp"
+#include "filter_compose.hpp"
 #include "../../include/catgrasp_amd.h"
 
 namespace {
 
-struct Limits { double up[7]; double lo[7]; };
-
-constexpr double D_BS = 0.36, D_SE = 0.42, D_EW = 0.4, D_WF = 0.081;
-constexpr double RHO2_MIN = 1e-6, C3_TOL = 1e-7, SINGULAR_EPS = 2e-3;
-
-// R <- R . (Rz(q) Rx(alpha)),  alpha = sgn * pi/2
-__device__ __forceinline__ void mul_link(double* R, double q, double sgn) {
-  const double c = cos(q), s = sin(q);
-  // Rz(q) Rx(alpha) = [[c, 0, s*sa], [s, 0, -c*sa], [0, sa, 0]] for cos(alpha) = 0, sa = sgn
-  double out[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double a = R[r * 3 + 0], b = R[r * 3 + 1], d = R[r * 3 + 2];
-    out[r * 3 + 0] = a * c + b * s;
-    out[r * 3 + 1] = d * sgn;
-    out[r * 3 + 2] = (a * s - b * c) * sgn;
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[k] = out[k];
-}
-
-__device__ __forceinline__ bool inside(double q, int j, const Limits& lim) { return q <= lim.up[j] && q >= lim.lo[j]; }
-
-__global__ __launch_bounds__(256) void iiwa_ik_kernel(const float* __restrict__ ee, long E, Limits lim, unsigned char* __restrict__ ok) {
+__global__ __launch_bounds__(256) void iiwa_ik_kernel(const float* __restrict__ ee, long E, cg_ik::IkLimits lim, unsigned char* __restrict__ ok) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
-  const float* T = ee + e * 16;
-  double R[9], p[3];
+  float T[16];
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
+  for (int k = 0; k < 16; ++k) T[k] = ee[e * 16 + k];
+  ok[e] = cg_ik::iiwa_ik_within_limits(T, lim) ? 1 : 0;
+}
+
+// The IK stage over a filter's segment table (filter_ik=True, common.cpp:214-226) without an (E,16) ee_in_base array in memory:
+// ee = cam_in_world . grasp_in_cam . ee_in_grasp is formed in registers with the mat4_mul order of the single-call ee_out pass
+// (collision.hip; -ffp-contract=off, so it is the float32 matrix that pass stores) and, where the approach test passed, goes through
+// the IK -> code 2 when no solution lies inside the limits.  The grid and exhaustive kernels then skip every code != 0.
+// EE_OUT (cg_filter_segments_ee_in_base, the pre-pass of a HOST solver): writes ee for every evaluation and codes {0, 1} instead.
+// (Here and not in collision.hip: like iiwa_ik_kernel it spills scalar registers to VGPR lanes -- the float64 trig keeps its constants
+// in SGPR pairs -- which the collision kernels are built never to do.  No scratch either way.)
+template <bool EE_OUT>
+__global__ __launch_bounds__(256) void compose_grasp_pose_multi_ik_kernel(cg_filter::ComposeMultiArgs a, cg_filter::MultiIkArgs k) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= a.E) return;
+  float gic[16], t2[16], ee[16];
+  int code = cg_filter::compose_multi(a, e, gic);
+  if (EE_OUT || code == 0) {
+    cg_filter::mat4_mul(k.cam_in_world.m, gic, t2);
+    cg_filter::mat4_mul(t2, k.ee_in_grasp.m, ee);
+  }
+  if constexpr (EE_OUT) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) R[r * 3 + c] = (double)T[r * 4 + c];
-    p[r] = (double)T[r * 4 + 3];
+    for (int q = 0; q < 16; q += 4) *(float4*)(k.ee_out + e * 16 + q) = *(float4*)(ee + q);
+    a.codes[e] = (signed char)code;
+  } else {
+    if (code == 0 && !cg_ik::iiwa_ik_within_limits(ee, k.lim)) code = 2;
+#pragma unroll
+    for (int q = 0; q < 16; q += 4) *(float4*)(a.poses_out + e * 16 + q) = *(float4*)(gic + q);
+    a.codes[e] = (signed char)code;
+    a.nudge[e] = (signed char)-1;
   }
-  const double wx = p[0] - D_WF * R[2], wy = p[1] - D_WF * R[5], wz = p[2] - D_WF * R[8];
-  const double rho0 = hypot(wx, wy), hh = wz - D_BS;
-  const double c3 = (rho0 * rho0 + hh * hh - D_SE * D_SE - D_EW * D_EW) / (2 * D_SE * D_EW);
-  bool found = false;
-  if (fabs(c3) <= 1.0 + C3_TOL && rho0 * rho0 >= RHO2_MIN && inside(0.0, 2, lim)) {
-    const double a3 = acos(fmin(1.0, fmax(-1.0, c3)));
-    for (int ib = 0; ib < 2 && !found; ++ib) {
-      const double sb = ib ? -1.0 : 1.0;
-      const double q0 = atan2(sb * wy, sb * wx);
-      if (!inside(q0, 0, lim)) continue;
-      for (int ie = 0; ie < 2 && !found; ++ie) {
-        const double q3 = (ie ? -1.0 : 1.0) * a3;
-        if (!inside(q3, 3, lim)) continue;
-        double q1 = atan2(sb * rho0, hh) + atan2(D_EW * sin(q3), D_SE + D_EW * cos(q3));
-        q1 = atan2(sin(q1), cos(q1));
-        if (!inside(q1, 1, lim)) continue;
-        double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        mul_link(A, q0, -1.0); mul_link(A, q1, 1.0); mul_link(A, 0.0, 1.0); mul_link(A, q3, -1.0);
-        // M = A^T R (only the entries the wrist needs)
-        const double m02 = A[0] * R[2] + A[3] * R[5] + A[6] * R[8];
-        const double m12 = A[1] * R[2] + A[4] * R[5] + A[7] * R[8];
-        const double m22 = A[2] * R[2] + A[5] * R[5] + A[8] * R[8];
-        const double m20 = A[2] * R[0] + A[5] * R[3] + A[8] * R[6];
-        const double m21 = A[2] * R[1] + A[5] * R[4] + A[8] * R[7];
-        const double c5 = fmin(1.0, fmax(-1.0, m22));
-        const double s5a = sqrt(fmax(0.0, 1.0 - c5 * c5));
-        if (s5a < SINGULAR_EPS) continue;
-        for (int iw = 0; iw < 2; ++iw) {
-          const double sw = iw ? -1.0 : 1.0;
-          const double q5 = atan2(sw * s5a, c5);
-          const double q4 = atan2(sw * m12, sw * m02);
-          const double q6 = atan2(sw * m21, -sw * m20);
-          if (inside(q4, 4, lim) && inside(q5, 5, lim) && inside(q6, 6, lim)) { found = true; break; }
-        }
-      }
-    }
-  }
-  ok[e] = found ? 1 : 0;
 }
 
 }  // namespace
+
+int cg_filter::launch_compose_multi_ik(const ComposeMultiArgs& a, const MultiIkArgs& k, bool ee_out, hipStream_t stream) {
+  const dim3 grid((unsigned)((a.E + 255) / 256));
+  if (ee_out) hipLaunchKernelGGL(compose_grasp_pose_multi_ik_kernel<true>, grid, dim3(256), 0, stream, a, k);
+  else hipLaunchKernelGGL(compose_grasp_pose_multi_ik_kernel<false>, grid, dim3(256), 0, stream, a, k);
+  return cg_hip_status(hipGetLastError());
+}
 
 extern "C" int cg_iiwa_ik_within_limits(const float* ee_in_base, long E, const double* h_upper7, const double* h_lower7,
                                         unsigned char* ok, void* stream) {
   if (E < 0 || !h_upper7 || !h_lower7) return CG_ERR_ARG;
   if (E == 0) return CG_OK;
   if (!ee_in_base || !ok) return CG_ERR_ARG;
-  Limits lim;
+  cg_ik::IkLimits lim;
   for (int j = 0; j < 7; ++j) { lim.up[j] = h_upper7[j]; lim.lo[j] = h_lower7[j]; }
   hipLaunchKernelGGL(iiwa_ik_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ee_in_base, E, lim, ok);
   return cg_hip_status(hipGetLastError());

@@ -366,12 +366,25 @@ class _FilterSegmentC(ctypes.Structure):
                 ('n_bg_keys', ctypes.c_int), ('reserved', ctypes.c_int), ('first', ctypes.c_longlong)]
 
 
+class _IkParamsC(ctypes.Structure):
+    """cg_iiwa_ik_params (include/catgrasp_amd.h)."""
+    _fields_ = [('cam_in_world', ctypes.c_float * 16), ('ee_in_grasp', ctypes.c_float * 16), ('upper', ctypes.c_double * 7),
+                ('lower', ctypes.c_double * 7)]
+
+
+def _ik_limits(upper, lower):
+    if upper is None or lower is None or len(upper) != 7 or len(lower) != 7:
+        raise ValueError('filter_ik=True needs the 7 upper and 7 lower joint limits')
+    return [float(v) for v in upper], [float(v) for v in lower]
+
+
 class FilterPlan:
     """Several filterGraspPose calls prepared as ONE launch sequence (cg_filter_grasp_pose_multi): the segment table on the host and its
     device copy.  segments: [(scene, grasp_poses (n,16) f32 cuda, symmetry_tfs (m,16) f32 cuda, nocs_pose 4x4, canonical_to_nocs 4x4,
     adjust_collision_pose)], all scenes on one device with the SAME gripper meshes and resolution (one gripper per run, as in the
     reference).  The plan keeps references to the tensors its table points at; build it once for a fixed set of calls (bench step,
-    pick cycle) and run it as often as needed -- run() itself moves no table and synchronises nothing."""
+    pick cycle) and run it as often as needed -- run() itself moves no table and synchronises nothing (except through a host IK solver,
+    see run)."""
 
     def __init__(self, segments):
         if not segments:
@@ -406,22 +419,72 @@ class FilterPlan:
         # one upload per plan, from page-locked memory so that it is queued behind the stream's work instead of waiting for it
         self._host = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).pin_memory()
         self.d_table = self._host.to(sc0.device, non_blocking=True)
+        # ... on the construction stream: a run on another stream (a plan built on one thread, run on another) waits for it
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record(torch.cuda.current_stream(sc0.device))
 
-    def run(self, gripper_in_grasp, filter_approach_dir_face_camera, keep_rejected_pose=False, work_stats=None, ik_ok=None):
-        """-> codes (E) int8, poses (E,4,4) float32, nudge (E) int8 over the plan's evaluations, segment after segment."""
+    def _wait_upload(self):
+        if self._uploaded is not None:
+            if self._uploaded.query():          # done: nothing to order any more
+                self._uploaded = None
+            else:
+                torch.cuda.current_stream(self.scene0.device).wait_event(self._uploaded)
+
+    def ee_in_base(self, cam_in_world, ee_in_grasp, filter_approach_dir_face_camera):
+        """The pre-IK pass over the whole table (cg_filter_segments_ee_in_base) -> ee_in_base (E,4,4) float32, codes (E) int8 {0, 1}:
+        cam_in_world . grasp_in_cam . ee_in_grasp of every evaluation, the pose a host IK solver judges."""
+        dev = self.scene0.device
+        ee = torch.empty((self.E, 16), dtype=torch.float32, device=dev)
+        codes = torch.empty((self.E,), dtype=torch.int8, device=dev)
+        if self.E:
+            self._wait_upload()
+            check(L.lib().cg_filter_segments_ee_in_base(self.table, _p(self.d_table), _c_int(self.n), _c_int(int(bool(filter_approach_dir_face_camera))),
+                                                        _h16(_mat4(cam_in_world, 'cam_in_world')), _h16(_mat4(ee_in_grasp, 'ee_in_grasp')),
+                                                        _p(ee), _p(codes), _stream()), 'cg_filter_segments_ee_in_base')
+        return ee.view(self.E, 4, 4), codes
+
+    def run(self, gripper_in_grasp, filter_approach_dir_face_camera, keep_rejected_pose=False, work_stats=None, ik_ok=None, ik=None):
+        """-> codes (E) int8, poses (E,4,4) float32, nudge (E) int8 over the plan's evaluations, segment after segment.
+        ik: dict(cam_in_world 4x4, ee_in_grasp 4x4, upper[7], lower[7]) -> filter_ik=True (common.cpp:214-226) for every evaluation,
+        bit-identical to filter_on_device(..., filter_ik=True) per segment.  The default solver (the device iiwa14 closed form) runs
+        inside the pose-composition launch (cg_filter_grasp_pose_multi_ik); with set_ik_solver(fn) active the plan runs the table-wide
+        pre-IK pass, calls fn on the host (a device-to-host copy and a synchronisation) and passes its verdicts as ik_ok.
+        ik_ok: a precomputed (E) uint8 device verdict instead (0 -> code 2)."""
         sc, dev = self.scene0, self.scene0.device
+        if ik is not None:
+            if ik_ok is not None:
+                raise ValueError('FilterPlan.run: pass ik or ik_ok, not both')
+            upper, lower = _ik_limits(ik.get('upper'), ik.get('lower'))
+            for k in ('cam_in_world', 'ee_in_grasp'):
+                if ik.get(k) is None:
+                    raise ValueError(f'FilterPlan.run: ik needs {k}')
         codes = torch.empty((self.E,), dtype=torch.int8, device=dev)
         poses = torch.empty((self.E, 16), dtype=torch.float32, device=dev)
         nudge = torch.empty((self.E,), dtype=torch.int8, device=dev)
         if self.E == 0:
             return codes, poses.view(0, 4, 4), nudge
+        self._wait_upload()
+        params = None
+        if ik is not None:
+            if _ik_solver is None:
+                params = _IkParamsC()
+                params.cam_in_world[:] = _mat4(ik['cam_in_world'], 'cam_in_world').reshape(16).tolist()
+                params.ee_in_grasp[:] = _mat4(ik['ee_in_grasp'], 'ee_in_grasp').reshape(16).tolist()
+                params.upper[:], params.lower[:] = upper, lower
+            else:
+                ee, _ = self.ee_in_base(ik['cam_in_world'], ik['ee_in_grasp'], filter_approach_dir_face_camera)
+                ok = np.asarray(_ik_solver(ee.cpu().numpy(), list(upper), list(lower))).astype(np.uint8).reshape(self.E)
+                ik_ok = torch.from_numpy(ok).to(dev)
         go = ctypes.byref(sc.grid_open.c) if sc.grid_open is not None else None
         ge = ctypes.byref(sc.grid_enc.c) if sc.grid_enc is not None else None
-        check(L.lib().cg_filter_grasp_pose_multi(self.table, _p(self.d_table), _c_int(self.n), _h16(_mat4(gripper_in_grasp, 'gripper_in_grasp')),
-                                                 _c_int(int(bool(filter_approach_dir_face_camera))), _p(ik_ok),
-                                                 _p(sc.V), _p(sc.F), _c_int(sc.F.shape[0]), _p(sc.Ve), _p(sc.Fe), _c_int(sc.Fe.shape[0]),
-                                                 ctypes.c_float(sc.res), _p(codes), _p(poses), _p(nudge), go, ge, _c_int(int(bool(keep_rejected_pose))),
-                                                 _p(work_stats), _stream()), 'cg_filter_grasp_pose_multi')
+        head = (self.table, _p(self.d_table), _c_int(self.n), _h16(_mat4(gripper_in_grasp, 'gripper_in_grasp')),
+                _c_int(int(bool(filter_approach_dir_face_camera))))
+        tail = (_p(sc.V), _p(sc.F), _c_int(sc.F.shape[0]), _p(sc.Ve), _p(sc.Fe), _c_int(sc.Fe.shape[0]),
+                ctypes.c_float(sc.res), _p(codes), _p(poses), _p(nudge), go, ge, _c_int(int(bool(keep_rejected_pose))), _p(work_stats), _stream())
+        if params is not None:
+            check(L.lib().cg_filter_grasp_pose_multi_ik(*head, ctypes.byref(params), *tail), 'cg_filter_grasp_pose_multi_ik')
+        else:
+            check(L.lib().cg_filter_grasp_pose_multi(*head, _p(ik_ok), *tail), 'cg_filter_grasp_pose_multi')
         return codes, poses.view(self.E, 4, 4), nudge
 
 

@@ -5,7 +5,7 @@
     background occupancy   my_cpp.makeOccupancyGridFromCloudScan          run_grasp_simulation.py:131-139
     NUNOCS + 9-D pose      NunocsPredicter.predict (net + device RANSAC)   :146
     candidates             grasp_sampler.cone_grasp_poses [+ canonical grasps x symmetries]   :176 -> grasp_sampler.py
-    collision/approach     my_cpp.filter_on_device                         grasp_sampler.py:216,345
+    collision/approach/IK  my_cpp.FilterPlan (filter_on_device per call)   grasp_sampler.py:216,345
     affordance P(T|G)      affordance.compute_grasp_affordance             :181
     grasp quality P(G)     GraspPredicter.score_on_device                  :310-313
     ranking                P(T,G) = P(T|G) P(G), descending                :314-329
@@ -140,32 +140,21 @@ def prepare_object(ob_pts, ob_normals, scene_pts, K, gripper, grasp_predicter, n
     scene = my_cpp.GripperScene(gripper['vertices'], gripper['faces'], gripper['enclosed_vertices'], gripper['enclosed_faces'], ob_pts, occ,
                                 resolution, dev)
     sym1 = torch.eye(4, device=dev).reshape(1, 16)
-    ee_in_grasp = I4 if ik is None else np.asarray(ik['ee_in_grasp'])
-    ik_kw = {} if ik is None else dict(upper=list(ik['upper']), lower=list(ik['lower']))
     with_canonical = canonical is not None and nocs_pose is not None and len(canonical.get('grasps', []))
     sym = symmetry_tfs if symmetry_tfs is not None else [np.eye(4)]
     cone16 = cone.float().reshape(-1, 16).contiguous()
-    if ik is None and cone16.shape[0] > 0:
-        # both call shapes of the object (grasp_sampler.py:216: cone poses, symmetry [I]; :345: canonical grasps x symmetries under the
-        # NUNOCS pose) as ONE launch sequence: each is a few thousand evaluations, a fraction of what fills the chip
-        rows = [(scene, cone16, sym1, I4, I4, True)]
-        if with_canonical:
-            f16 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64), dtype=np.float32).reshape(-1, 16)).to(dev)
-            rows.append((scene, f16(canonical['grasps']), f16(sym), nocs_pose, I4, True))
-        plan = my_cpp.FilterPlan(rows)
-        codes, poses, _ = plan.run(gripper['gripper_in_grasp'], True)
-        surv = [poses[codes == 0]]
-        n_evaluated = plan.E
-    else:               # with the IK stage (its pre-pass computes ee_in_base per call) the calls stay separate
-        codes, poses, _ = my_cpp.filter_on_device(scene, cone16, sym1, I4, I4, cam_in_world, ee_in_grasp,
-                                                  gripper['gripper_in_grasp'], True, ik is not None, True, **ik_kw)
-        keep = codes == 0
-        surv = [poses[keep]]
-        n_evaluated = int(codes.numel())
-        if with_canonical:
-            c2, p2, _ = my_cpp.filter_on_device(scene, np.asarray(canonical['grasps']), np.asarray(sym), nocs_pose, I4, cam_in_world, ee_in_grasp,
-                                                gripper['gripper_in_grasp'], True, ik is not None, True, **ik_kw)
-            surv.append(p2[c2 == 0]); n_evaluated += int(c2.numel())
+    # both call shapes of the object (grasp_sampler.py:216: cone poses, symmetry [I]; :345: canonical grasps x symmetries under the
+    # NUNOCS pose) as ONE launch sequence: each is a few thousand evaluations, a fraction of what fills the chip.  With `ik` the IK stage
+    # runs inside it (FilterPlan.run(ik=...)), every evaluation bit-identical to its own filter_ik=True call.
+    rows = [(scene, cone16, sym1, I4, I4, True)]
+    if with_canonical:
+        f16 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64), dtype=np.float32).reshape(-1, 16)).to(dev)
+        rows.append((scene, f16(canonical['grasps']), f16(sym), nocs_pose, I4, True))
+    plan = my_cpp.FilterPlan(rows)
+    ik_run = None if ik is None else dict(cam_in_world=cam_in_world, ee_in_grasp=ik['ee_in_grasp'], upper=ik.get('upper'), lower=ik.get('lower'))
+    codes, poses, _ = plan.run(gripper['gripper_in_grasp'], True, ik=ik_run)
+    surv = [poses[codes == 0]]
+    n_evaluated = plan.E
     surv = torch.cat(surv).contiguous()
     lap('filterGraspPose', t0)
     n = surv.shape[0]
@@ -266,13 +255,15 @@ def evaluate_objects(objects, scene_pts, K, gripper, grasp_predicter, nunocs_pre
       'draws'  -- round 5's form: only the next object's NUNOCS-stage draws (~80 ms of sequential host work: numpy's Fisher-Yates
           rejection walk) are made ahead, on a second thread; NunocsPredicter.predict takes them only if numpy's generator really
           stands where they started.
-      None     -- the serial loop."""
+      None     -- the serial loop.
+    With `ik` (filter_ik=True) the default is the same: the IK stage draws nothing from numpy's stream, so the explicit-state replay above
+    still holds.  A host IK solver registered with my_cpp.set_ik_solver is then called from the stages thread."""
     from . import engine
     from . import predicter as pred_mod
     rng = kw.get('rng') or getattr(grasp_predicter, 'rng', 'device')
     can_predraw = bool(getattr(nunocs_predicter, '_predraw', False))
     if overlap is None:
-        overlap = 'stages' if (draw_ahead and can_predraw and kw.get('ik') is None) else None
+        overlap = 'stages' if (draw_ahead and can_predraw) else None
     if overlap == 'stages' and not can_predraw:
         overlap = None
     if overlap == 'draws' and not (rng == 'numpy' and can_predraw):

@@ -176,16 +176,18 @@ class SceneBatch:
     # 'multi': the filter calls of a slice as ONE launch sequence (run_filter_many); 'per_segment': one filterGraspPose call per (object,
     # call shape) on the objects' side streams -- the round-5 form, kept for the equality test (tests/test_workload_gpu.py)
     filter_launch = 'multi'
+    # filter_ik=True (opt-in, bench.py does not set it): dict(cam_in_world 4x4, ee_in_grasp 4x4, upper[7], lower[7]) -- see FilterPlan.run
+    ik = None
 
     def __init__(self, device, grasp_predicter, nunocs_predicter, kind='nut', n_objects=8, pts_per_object=2500, per_replica=50000,
-                 replicas=1, scene_seed=0, nocs_scale=0.02, materialize=None, gripper_subdivisions=0):
+                 replicas=1, scene_seed=0, nocs_scale=0.02, materialize=None, gripper_subdivisions=0, ik=None):
         # materialize: (lo, hi) global evaluation range whose candidate poses are generated up front (default: all)
         # kind: one category ('nut' | 'hnm' | 'screw'), or a mixed bin of synth.MIXED_BINS ('bin' = nut + hnm + screw, BASELINE.json
         # configs[4]); for a mixed bin the two predicters are dicts {category: predicter} -- the reference keeps one GraspPredicter /
         # NunocsPredicter per class (run_grasp_simulation.py:701-702), each with its own weights.
         import torch
         from . import my_cpp, synth, transforms
-        self.device, self.kind = device, kind
+        self.device, self.kind, self.ik = device, kind, ik
         self.objs = synth.make_scene(n_objects, pts_per_object, seed=scene_seed, kind=kind)       # same scene on every rank
         # gripper_subdivisions: 0 = the 36 / 48-triangle box gripper, 4 = the same surfaces as 9,216 / 12,288 triangles (bench.py)
         self.gripper = synth.make_gripper(subdivisions=gripper_subdivisions)
@@ -260,8 +262,10 @@ class SceneBatch:
             sym, nocs = self.syms[self.cats[seg.obj]][j0:j1], self.nocs_pose[seg.obj]
         else:
             sym, nocs = self.eye, I4
-        codes, poses, _ = my_cpp.filter_on_device(self.scenes[seg.obj], self.segment_poses(seg)[i0:i1], sym, nocs, I4, I4, I4,
-                                                  g['gripper_in_grasp'], True, False, seg.adjust, keep_rejected_pose=True)
+        ik = self.ik or {}
+        codes, poses, _ = my_cpp.filter_on_device(self.scenes[seg.obj], self.segment_poses(seg)[i0:i1], sym, nocs, I4,
+                                                  ik.get('cam_in_world', I4), ik.get('ee_in_grasp', I4), g['gripper_in_grasp'], True,
+                                                  self.ik is not None, seg.adjust, ik.get('upper'), ik.get('lower'), keep_rejected_pose=True)
         return codes, poses.view(-1, 16)
 
     def run_filter_many(self, key, rects):
@@ -280,7 +284,7 @@ class SceneBatch:
                     sym, nocs = self.eye, I4
                 rows.append((self.scenes[s.obj], self.segment_poses(s)[i0:i1], sym, nocs, I4, s.adjust))
             plan = self._plans[key] = my_cpp.FilterPlan(rows)
-        codes, poses, _ = plan.run(self.gripper['gripper_in_grasp'], True, keep_rejected_pose=True)
+        codes, poses, _ = plan.run(self.gripper['gripper_in_grasp'], True, keep_rejected_pose=True, ik=self.ik)
         return codes, poses.view(-1, 16)
 
     def run_prep(self, obj, poses, row_offset, pinv_out, ids_out):

@@ -262,7 +262,8 @@ int cg_filter_grasp_pose_accel(const float* grasp_poses, int n_pose, const float
  *     float32 operation order of the single-call path, writes `first`; returns the total number of evaluations or a negative cg error.
  *   cg_filter_grasp_pose_multi: h_segments = the prepared HOST table, d_segments = a DEVICE copy of those same n_segments rows (the
  *     caller uploads it however it likes -- a cached upload costs nothing per call -- and keeps it alive until the stream has passed
- *     the call).  No pre-IK stage here (ee_in_base): a caller that filters by IK runs that stage per segment and passes ik_ok. */
+ *     the call).  ik_ok (optional, E bytes, 0 => code 2) is a precomputed IK verdict; cg_filter_grasp_pose_multi_ik below runs the IK
+ *     stage itself. */
 typedef struct cg_filter_segment {
   const float* grasp_poses;        /* device (n_pose,16), 16-byte aligned */
   const float* symmetry_tfs;       /* device (n_sym,16), 16-byte aligned */
@@ -288,6 +289,33 @@ int cg_filter_grasp_pose_multi(const cg_filter_segment* h_segments, const cg_fil
                                float resolution, signed char* codes, float* poses_out, signed char* nudge,
                                const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, int keep_rejected_pose,
                                unsigned long long* work_stats, void* stream);
+/* filter_ik=True over a prepared table (common.cpp:214-226).  cam_in_world / ee_in_grasp: row-major 4x4 (common to the launch, as in the
+ * reference: one robot and one camera per run); upper / lower: the 7 joint limits (rad) of the KUKA LBR iiwa14 (see
+ * cg_iiwa_ik_within_limits).
+ *   cg_filter_grasp_pose_multi_ik: cg_filter_grasp_pose_multi with the device iiwa14 IK instead of ik_ok.  Three launches: the pose
+ *     composition forms ee_in_base = cam_in_world . grasp_in_cam . ee_in_grasp in registers for every evaluation the approach test passed
+ *     and runs the closed-form IK on it (code 2: no solution inside the limits) -- no ee_in_base array is stored -- then the grid and the
+ *     exhaustive kernel.  Every evaluation's result is bit-identical to its own filter_ik=True call (pre-IK pass, cg_iiwa_ik_within_limits,
+ *     cg_filter_grasp_pose_accel with that ik_ok).  h_ik: HOST.
+ *   cg_filter_segments_ee_in_base: the table-wide pre-IK pass a HOST IK solver needs: ee_out (E,16) f32 DEVICE (16-byte aligned),
+ *     ee_in_base of every evaluation, and codes (E) {0, 1} (the approach test).  Its verdicts then go to cg_filter_grasp_pose_multi as
+ *     ik_ok. */
+typedef struct cg_iiwa_ik_params {
+  float cam_in_world[16];
+  float ee_in_grasp[16];
+  double upper[7];
+  double lower[7];
+} cg_iiwa_ik_params;
+int cg_filter_grasp_pose_multi_ik(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
+                                  const float* h_gripper_in_grasp, int filter_approach_dir_face_camera, const cg_iiwa_ik_params* h_ik,
+                                  const float* gripper_vertices, const int* gripper_faces, int n_gripper_faces,
+                                  const float* enclosed_vertices, const int* enclosed_faces, int n_enclosed_faces,
+                                  float resolution, signed char* codes, float* poses_out, signed char* nudge,
+                                  const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, int keep_rejected_pose,
+                                  unsigned long long* work_stats, void* stream);
+int cg_filter_segments_ee_in_base(const cg_filter_segment* h_segments, const cg_filter_segment* d_segments, int n_segments,
+                                  int filter_approach_dir_face_camera, const float* h_cam_in_world, const float* h_ee_in_grasp,
+                                  float* ee_out, signed char* codes, void* stream);
 
 /* Device build of cg_mesh_grid (replaces a per-triangle host loop): triangle t is listed in every cell its bounding box,
  * inflated by `inflate`, overlaps (float64 cell arithmetic).  h_origin[3], h_dims[3]: HOST.  Two passes around a host-side
