@@ -38,7 +38,11 @@ __global__ __launch_bounds__(256) void build_grasp_input_kernel(
   const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 2;
   if (i >= total) return;
   float v[12];
-  if (i + 1 < total && (n_pts & 1) == 0) {          // the pair lies inside one candidate and is 8-byte aligned
+  // the launcher sends every call here whose pointers are not 16-byte aligned, so the vector accesses below are taken only when
+  // they are aligned themselves: i is even, so ids + i is 8-byte aligned iff ids is, and out + 6 i (48-byte steps) is 16-byte
+  // aligned iff out is.  Any other call takes the scalar path (wave-uniform choice; same fmaf chain, same bytes).
+  const bool vec = (((uintptr_t)ids & 7) | ((uintptr_t)out & 15)) == 0;
+  if (vec && i + 1 < total && (n_pts & 1) == 0) {   // the pair lies inside one candidate and is 8-byte aligned
     const int2 id = *(const int2*)(ids + i);
     const float* T = pose_inv + (size_t)(i / n_pts) * 12;
     grasp_point(xyz, nrm, id.x, T, mean, inv_std, v);
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(256) void build_grasp_input_kernel(
     o[0] = f32x4{v[0], v[1], v[2], v[3]}; o[1] = f32x4{v[4], v[5], v[6], v[7]}; o[2] = f32x4{v[8], v[9], v[10], v[11]};
     return;
   }
-  for (long k = i; k < total && k < i + 2; ++k) {   // odd n_pts: scalar path
+  for (long k = i; k < total && k < i + 2; ++k) {   // odd n_pts, the last single point, or unaligned ids / out: scalar path
     grasp_point(xyz, nrm, ids[k], pose_inv + (size_t)(k / n_pts) * 12, mean, inv_std, v);
     for (int j = 0; j < 6; ++j) out[k * 6 + j] = v[j];
   }

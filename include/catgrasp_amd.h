@@ -144,7 +144,8 @@ int cg_nunocs_decode(const float* logits, long P, int nbins, float* coords, floa
 /* GraspDataset.transform (dataset_grasp.py:63-91) for G candidates at once.
  * cloud_xyz/cloud_normal: (n_cloud,3) f32 (z>=0.1 filtered, object-centred by the host);
  * ids: (G,n_pts) i32 resample indices into the cloud; pose_inv: (G,12) rows of inv(grasp_pose)[:3,:4]
- * (re-expressed for the centred cloud); mean / inv_std: (6) or both NULL.  out: (G,n_pts,6). */
+ * (re-expressed for the centred cloud); mean / inv_std: (6) or both NULL.  out: (G,n_pts,6).
+ * Pointers need only the alignment of their element type (16-byte aligned ids / out / clouds take the faster kernels). */
 int cg_build_grasp_input(const float* cloud_xyz, const float* cloud_normal, int n_cloud, const int* ids,
                          const float* pose_inv, const float* mean, const float* inv_std, int G, int n_pts,
                          float* out, void* stream);

@@ -66,6 +66,11 @@ def test_build_grasp_input_kernel(cuda_device):
     ref = np.stack([tref.grasp_transform(ob['xyz'].copy(), ob['normal'].copy(), P[i], ids[i], mean, std)['input'] for i in range(len(P))])
     # float32 evaluation of a float64 formula: ~1e-6 of the value range
     assert np.abs(x - ref).max() <= 2e-5 * np.abs(ref).max()
+    # and per element: bit for bit the float32 chain, within the derived bound of float64 (tests/prep_ref.py)
+    import prep_ref
+    case = {'xyz64': ob['xyz'], 'nrm64': ob['normal'], 'xyz32': dc.xyz.cpu().numpy(), 'nrm32': dc.normal.cpu().numpy(), 'poses': P,
+            'T12': pinv.cpu().numpy(), 'ids': ids, 'mean64': mean, 'std64': std, 'mean32': m.cpu().numpy(), 'inv_std32': s.cpu().numpy()}
+    assert prep_ref.check_grasp(case, x, 'build_grasp_input') <= 1.0
 
 
 def test_nunocs_predict_nocs(cuda_device):
