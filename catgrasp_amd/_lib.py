@@ -2,6 +2,13 @@
 
 The HIP library is the product: there is no CPU fallback.  `lib()` raises if the shared object
 is missing or does not export every declared symbol; every wrapper raises on a non-zero status.
+
+The header is the one statement of every prototype: `lib()` sets `argtypes` and `restype` of every entry point from it, so
+call sites pass plain Python numbers and ctypes converts -- and refuses -- them per parameter: a missing argument is a
+TypeError; a float for an integer, a list for a pointer or a ctypes scalar of another type than declared is a
+ctypes.ArgumentError; a count >= 2**31 for a `long` arrives intact.  Every pointer parameter is a c_void_p: it takes `_p(tensor)`,
+None, an address, `byref(struct)` and ctypes arrays.  Two things ctypes does NOT catch: extra trailing arguments are passed
+through, and a `str` is accepted for a pointer.
 """
 import ctypes
 import os
@@ -14,17 +21,47 @@ LIB_PATH = os.environ.get('CATGRASP_AMD_LIB', os.path.join(_PKG, 'libcatgrasp_am
 HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd.h')
 _lib = None
 
+_SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
+            'unsigned long long': ctypes.c_ulonglong, 'size_t': ctypes.c_size_t}
+_PROTOTYPE = re.compile(r'([\w\s*]+?)\b(cg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;')
+
 
 class CatgraspAmdError(RuntimeError):
     pass
 
 
+def _ctype(decl, what, ret=False):
+    t = ' '.join(decl.replace('*', ' * ').split())
+    c = ctypes.c_char_p if ret and t == 'const char *' else ctypes.c_void_p if '*' in t else _SCALARS.get(t)
+    if c is None:
+        raise CatgraspAmdError(f'include/catgrasp_amd.h: {what} has type {t!r}, which the binding does not map')
+    return c
+
+
+def signatures(src=None):
+    """{name: (restype, argtypes)} of every function declared in include/catgrasp_amd.h (or in the header text `src`).  A parser for
+    THIS header, not for C: comments, preprocessor lines and `typedef struct {...}` blocks are dropped, the rest must be prototypes
+    of scalars and pointers inside the `extern "C"` braces; anything else raises."""
+    if src is None:
+        with open(HEADER_PATH) as f:
+            src = f.read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    src = re.sub(r'^\s*#.*$', '', src, flags=re.M)
+    src = re.sub(r'\btypedef\s+struct\b[^{}]*\{[^{}]*\}[^;]*;', '', src)
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(src):
+        params = [] if params.strip() == 'void' else [p.strip() for p in params.split(',')]
+        sigs[name] = (_ctype(ret, f'the return value of {name}', ret=True),
+                      tuple(_ctype(re.sub(r'\w+$', '', p), f'parameter {p!r} of {name}') for p in params))
+    rest = _PROTOTYPE.sub('', src).replace('extern "C" {', '', 1).replace('}', '', 1).strip()
+    if rest:
+        raise CatgraspAmdError(f'include/catgrasp_amd.h: the binding cannot parse {rest[:200]!r}')
+    return sigs
+
+
 def declared_symbols():
     """Names of every function declared in include/catgrasp_amd.h."""
-    with open(HEADER_PATH) as f:
-        src = f.read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(cg_[a-z0-9_]+)\s*\(', src)))
+    return sorted(signatures())
 
 
 def lib():
@@ -35,10 +72,13 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -m catgrasp_amd.build` '
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
-        missing = [s for s in declared_symbols() if not hasattr(l, s)]
+        sigs = signatures()
+        missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')
-        l.cg_version.restype = ctypes.c_char_p
+        for name, (restype, argtypes) in sigs.items():
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = l
     return _lib
 

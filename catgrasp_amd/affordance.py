@@ -9,9 +9,6 @@ import torch
 from . import _lib as L
 from ._lib import _p, _stream, check
 
-_c_int = ctypes.c_int
-_c_long = ctypes.c_long
-
 
 def _device(device):
     if device is not None:
@@ -27,7 +24,7 @@ def nearest_neighbor(query, ref, device=None):
     q = torch.from_numpy(np.ascontiguousarray(np.asarray(query, dtype=np.float64).reshape(-1, 3))).to(dev)
     r = torch.from_numpy(np.ascontiguousarray(np.asarray(ref, dtype=np.float64).reshape(-1, 3))).to(dev)
     idx = torch.empty((q.shape[0],), dtype=torch.int32, device=dev)
-    check(L.lib().cg_nearest_neighbor(_p(q), _c_long(q.shape[0]), _p(r), _c_int(r.shape[0]), _p(idx), _stream()), 'cg_nearest_neighbor')
+    check(L.lib().cg_nearest_neighbor(_p(q), q.shape[0], _p(r), r.shape[0], _p(idx), _stream()), 'cg_nearest_neighbor')
     return idx
 
 
@@ -71,8 +68,7 @@ def compute_grasp_affordance(model, grasp_poses_in_cam, finger_mesh_in_grasp, fi
     counts = torch.zeros((G, nf), dtype=torch.int32, device=dev) if return_counts else None
     E = (ctypes.c_double * (4 * nf))(*[float(v) for v in ext])
     S = (ctypes.c_int * nf)(*signs)
-    check(L.lib().cg_grasp_affordance(_p(d_cif), _c_long(G), _p(model.pts), _p(model.normals), _p(model.aff), _c_int(model.pts.shape[0]),
-                                      _c_int(nf), E, S, ctypes.c_double(float(surface_tol)), _p(out), _p(counts), _stream()),
-          'cg_grasp_affordance')
+    check(L.lib().cg_grasp_affordance(_p(d_cif), G, _p(model.pts), _p(model.normals), _p(model.aff), model.pts.shape[0], nf, E, S, float(surface_tol),
+                                      _p(out), _p(counts), _stream()), 'cg_grasp_affordance')
     res = out.cpu().numpy()
     return (res, counts.cpu().numpy()) if return_counts else res

@@ -8,8 +8,6 @@ import torch
 from . import _lib as L
 from ._lib import _p, _stream, check
 
-_c_int = ctypes.c_int
-
 
 def draw_hypothesis_ids(n_points, max_iter):
     """The reference's sampling (aligning.py:89-93): one `np.random.choice(n, size=4, replace=False)` per iteration from
@@ -55,7 +53,7 @@ def voxel_down_sample_device(pts, voxel_size):
 def _nn_dist(query, ref):
     """cKDTree(ref).query(query)[0] on the device: brute-force float64 nearest neighbour (cg_nearest_neighbor) + the distance."""
     idx = torch.empty((query.shape[0],), dtype=torch.int32, device=query.device)
-    check(L.lib().cg_nearest_neighbor(_p(query), ctypes.c_long(query.shape[0]), _p(ref), _c_int(ref.shape[0]), _p(idx), _stream()), 'cg_nearest_neighbor')
+    check(L.lib().cg_nearest_neighbor(_p(query), query.shape[0], _p(ref), ref.shape[0], _p(idx), _stream()), 'cg_nearest_neighbor')
     return torch.linalg.vector_norm(query - ref[idx.long()], dim=1)
 
 
@@ -112,7 +110,7 @@ def estimate9DTransform(source, target, PassThreshold, max_iter=1000, use_kdtree
     mn = D3(*[float(v) for v in np.asarray(min_scale, dtype=np.float64).reshape(3)])
     mx = D3(*[float(v) for v in np.asarray(max_scale, dtype=np.float64).reshape(3)])
     md = D3(*[float(v) for v in np.asarray(max_dimensions, dtype=np.float64).reshape(3)]) if max_dimensions is not None else None
-    check(L.lib().cg_ransac_9d(_p(d_src), _p(d_dst), _c_int(N), _p(d_ids), _c_int(H), ctypes.c_double(float(PassThreshold)), mn, mx, md,
+    check(L.lib().cg_ransac_9d(_p(d_src), _p(d_dst), N, _p(d_ids), H, float(PassThreshold), mn, mx, md,
                                _p(counts), _p(transforms), _stream()), 'cg_ransac_9d')
     c = counts.cpu().numpy()
     valid = c >= 0
@@ -123,7 +121,7 @@ def estimate9DTransform(source, target, PassThreshold, max_iter=1000, use_kdtree
     # ratios = count/N over the accepted hypotheses, arg-max = first maximum (aligning.py:112)
     best = int(np.flatnonzero(valid)[np.argmax(c[valid])])
     mask = torch.empty((N,), dtype=torch.uint8, device=device)
-    check(L.lib().cg_similarity_inliers(_p(d_src), _p(d_dst), _c_int(N), _p(transforms[best]), ctypes.c_double(float(PassThreshold)), _p(mask),
+    check(L.lib().cg_similarity_inliers(_p(d_src), _p(d_dst), N, _p(transforms[best]), float(PassThreshold), _p(mask),
                                         _stream()), 'cg_similarity_inliers')
     T = transforms[best].cpu().numpy().reshape(4, 4).copy()
     return T, np.where(mask.cpu().numpy() > 0)[0]

@@ -314,12 +314,10 @@ def _cls_forward_one_call(W, x):
         W._cls_c = cached = (ptrs, cw)
     cw = cached[1]
     lib = L.lib()
-    if lib.cg_pointnet_cls_workspace_floats.restype is not ctypes.c_size_t:
-        lib.cg_pointnet_cls_workspace_floats.restype = ctypes.c_size_t
-    ws = torch.empty((lib.cg_pointnet_cls_workspace_floats(ctypes.c_int(B)),), dtype=torch.float32, device=x.device)
+    ws = torch.empty((lib.cg_pointnet_cls_workspace_floats(B),), dtype=torch.float32, device=x.device)
     logits = torch.empty((B, W.n_out), dtype=torch.float32, device=x.device)
     tf = ctypes.c_void_p(0)
-    L.check(lib.cg_pointnet_cls_forward(L._p(x), ctypes.c_int(B), ctypes.c_int(N), ctypes.byref(cw), ctypes.c_int(_nsplit(B, N)), L._p(ws), L._p(logits),
+    L.check(lib.cg_pointnet_cls_forward(L._p(x), B, N, ctypes.byref(cw), _nsplit(B, N), L._p(ws), L._p(logits),
                                         ctypes.byref(tf), L._stream()), 'cg_pointnet_cls_forward')
     off = (tf.value - ws.data_ptr()) // 4
     t64 = ws[off:off + B * 4096]

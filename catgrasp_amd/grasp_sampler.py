@@ -2,16 +2,12 @@
 (dexnet/grasping/grasp_sampler.py:155-298): per sampled surface point a local frame from the neighbours' normals, then the
 fan-out over approach directions x in-plane rotations x approach depths; optionally centred between the fingers.
 Returns poses only; filtering is `catgrasp_amd.my_cpp.filterGraspPose`."""
-import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from ._lib import _p, _stream, check
-
-_c_int = ctypes.c_int
-_c_long = ctypes.c_long
 
 
 def cone_grasp_poses(points_for_sample, normals_for_sample, sample_ids, sphere_pts, r_ball, hand_depth, init_bite, approach_step,
@@ -36,21 +32,18 @@ def cone_grasp_poses(points_for_sample, normals_for_sample, sample_ids, sphere_p
         return out.view(0, 4, 4) if return_tensor else out.view(0, 4, 4).cpu().numpy()
     lib = L.lib()
     dbl = torch.zeros((K,), dtype=torch.int32, device=device)
-    check(lib.cg_cone_frames(_p(pts), _p(nrm), _c_int(P), _p(ids), _c_int(K), None, ctypes.c_double(float(r_ball)), _c_int(0), _p(dbl), None,
-                             _stream()), 'cg_cone_frames')
+    check(lib.cg_cone_frames(_p(pts), _p(nrm), P, _p(ids), K, None, float(r_ball), 0, _p(dbl), None, _stream()), 'cg_cone_frames')
     # the reference mutates self.params['r_ball'] while it walks the points in order: radius of point k = r0 * 2^(max doublings so far)
     radii = float(r_ball) * np.power(2.0, np.maximum.accumulate(dbl.cpu().numpy().astype(np.float64)))
     d_r = torch.from_numpy(radii).to(device)
     if info is not None:
         info['radii'] = radii               # ball radius used at each sample point (after the reference's persistent doublings)
     frames = torch.empty((K, 9), dtype=torch.float64, device=device)
-    check(lib.cg_cone_frames(_p(pts), _p(nrm), _c_int(P), _p(ids), _c_int(K), _p(d_r), ctypes.c_double(float(r_ball)), _c_int(1), None, _p(frames),
-                             _stream()), 'cg_cone_frames')
-    check(lib.cg_cone_poses(_p(pts), _p(ids), _p(frames), _c_int(K), _p(sph), _c_int(S), _c_int(n_rot), ctypes.c_double(float(inplane_step_deg)),
-                            _c_int(n_depth), ctypes.c_double(float(approach_step)), ctypes.c_double(float(init_bite)), _p(out), _stream()),
-          'cg_cone_poses')
+    check(lib.cg_cone_frames(_p(pts), _p(nrm), P, _p(ids), K, _p(d_r), float(r_ball), 1, None, _p(frames), _stream()), 'cg_cone_frames')
+    check(lib.cg_cone_poses(_p(pts), _p(ids), _p(frames), K, _p(sph), S, n_rot, float(inplane_step_deg), n_depth, float(approach_step),
+                            float(init_bite), _p(out), _stream()), 'cg_cone_poses')
     if center_ob_between_gripper:
-        check(lib.cg_center_grasps(_p(out), _c_long(total), _p(pts), _c_int(P), _stream()), 'cg_center_grasps')
+        check(lib.cg_center_grasps(_p(out), total, _p(pts), P, _stream()), 'cg_center_grasps')
     out = out.view(total, 4, 4)
     return out if return_tensor else out.cpu().numpy()
 

@@ -23,8 +23,6 @@ import torch
 from . import _lib as L
 from ._lib import _p, _stream, check
 
-_c_int = ctypes.c_int
-_c_long = ctypes.c_long
 _F16 = ctypes.c_float * 16
 
 _ik_solver = None
@@ -47,7 +45,7 @@ def ik_within_limits_device(ee, upper, lower):
     up = (ctypes.c_double * 7)(*[float(v) for v in upper])
     lo = (ctypes.c_double * 7)(*[float(v) for v in lower])
     ok = torch.empty((E,), dtype=torch.uint8, device=ee.device)
-    check(L.lib().cg_iiwa_ik_within_limits(_p(ee), ctypes.c_long(E), up, lo, _p(ok), _stream()), 'cg_iiwa_ik_within_limits')
+    check(L.lib().cg_iiwa_ik_within_limits(_p(ee), E, up, lo, _p(ok), _stream()), 'cg_iiwa_ik_within_limits')
     return ok
 
 
@@ -94,12 +92,12 @@ def voxelize(pts, resolution, device=None):
         raise ValueError(f'point cloud shape wrong: {tuple(t.shape)}')
     P = t.shape[0]
     packed = torch.empty((P,), dtype=torch.int64, device=device)
-    check(L.lib().cg_voxel_keys(_p(t), _c_long(P), ctypes.c_float(resolution), _p(packed), _stream()), 'cg_voxel_keys')
+    check(L.lib().cg_voxel_keys(_p(t), P, resolution, _p(packed), _stream()), 'cg_voxel_keys')
     uniq = torch.unique(packed)            # sorted
     uniq = uniq[uniq >= 0].contiguous()
     n = uniq.shape[0]
     keys = torch.empty((n, 4), dtype=torch.int16, device=device)
-    check(L.lib().cg_unpack_voxel_keys(_p(uniq), _c_long(n), _p(keys), _stream()), 'cg_unpack_voxel_keys')
+    check(L.lib().cg_unpack_voxel_keys(_p(uniq), n, _p(keys), _stream()), 'cg_unpack_voxel_keys')
     return keys
 
 
@@ -170,22 +168,20 @@ class CollisionManager:
         # the pose tensors stay referenced until the launch is queued: a temporary's block would be handed to the next allocation
         if a['kind'] == 'mesh' and b['kind'] == 'mesh':
             pa, pb = self._dev_pose(a['pose']), self._dev_pose(b['pose'])
-            check(L.lib().cg_mesh_mesh_collide(_p(a['V']), _p(a['F']), _c_int(a['F'].shape[0]), _p(b['V']), _p(b['F']), _c_int(b['F'].shape[0]),
+            check(L.lib().cg_mesh_mesh_collide(_p(a['V']), _p(a['F']), a['F'].shape[0], _p(b['V']), _p(b['F']), b['F'].shape[0],
                                                _p(pa), _p(pb), _p(out), _stream()), 'cg_mesh_mesh_collide')
         elif a['kind'] == 'cloud' and b['kind'] == 'cloud':
             rel = self._dev_pose((np.linalg.inv(a['pose'].astype(np.float64)) @ b['pose'].astype(np.float64)).astype(np.float32))
-            check(L.lib().cg_voxels_voxels_collide(_p(a['keys']), _c_int(a['keys'].shape[0]), ctypes.c_float(a['res']), _p(b['keys']),
-                                                   _c_int(b['keys'].shape[0]), ctypes.c_float(b['res']), _p(rel), _p(out), _stream()),
-                  'cg_voxels_voxels_collide')
+            check(L.lib().cg_voxels_voxels_collide(_p(a['keys']), a['keys'].shape[0], a['res'], _p(b['keys']), b['keys'].shape[0], b['res'],
+                                                   _p(rel), _p(out), _stream()), 'cg_voxels_voxels_collide')
         else:
             mesh, cloud = (a, b) if a['kind'] == 'mesh' else (b, a)
             rel = mesh['pose']
             if not np.array_equal(cloud['pose'], np.eye(4, dtype=np.float32)):        # the mesh as seen from the cloud's frame
                 rel = (np.linalg.inv(cloud['pose'].astype(np.float64)) @ mesh['pose'].astype(np.float64)).astype(np.float32)
             rel = self._dev_pose(rel)
-            check(L.lib().cg_mesh_voxels_collide(_p(mesh['V']), _p(mesh['F']), _c_int(mesh['F'].shape[0]), _p(rel), _c_long(1),
-                                                 _p(cloud['keys']), _c_int(cloud['keys'].shape[0]), ctypes.c_float(cloud['res']),
-                                                 _p(out), _stream()), 'cg_mesh_voxels_collide')
+            check(L.lib().cg_mesh_voxels_collide(_p(mesh['V']), _p(mesh['F']), mesh['F'].shape[0], _p(rel), 1, _p(cloud['keys']),
+                                                 cloud['keys'].shape[0], cloud['res'], _p(out), _stream()), 'cg_mesh_voxels_collide')
         return bool(out.item())
 
     def isAnyCollision(self):
@@ -230,15 +226,14 @@ class MeshGrid:
             org = (ctypes.c_double * 3)(*[float(v) for v in lo])
             dm = (ctypes.c_int * 3)(*[int(v) for v in dims])
             counts = torch.zeros((ncell,), dtype=torch.int32, device=device)
-            check(L.lib().cg_mesh_grid_count(_p(Vd), _p(Fd), _c_int(len(F)), org, ctypes.c_double(cell), ctypes.c_double(inflate), dm,
-                                             _p(counts), _stream()), 'cg_mesh_grid_count')
+            check(L.lib().cg_mesh_grid_count(_p(Vd), _p(Fd), len(F), org, cell, inflate, dm, _p(counts), _stream()), 'cg_mesh_grid_count')
             start = torch.zeros((ncell + 1,), dtype=torch.int32, device=device)
             torch.cumsum(counts, 0, out=start[1:])
             self.n_entries = int(start[-1].item())
             self.cell_start = start
             self.tri_ids = torch.empty((max(self.n_entries, 1),), dtype=torch.int32, device=device)
             counts.zero_()
-            check(L.lib().cg_mesh_grid_fill(_p(Vd), _p(Fd), _c_int(len(F)), org, ctypes.c_double(cell), ctypes.c_double(inflate), dm,
+            check(L.lib().cg_mesh_grid_fill(_p(Vd), _p(Fd), len(F), org, cell, inflate, dm,
                                             _p(start), _p(counts), _p(self.tri_ids), _stream()), 'cg_mesh_grid_fill')
         # the triangles as a flat (nf,12) array [v0 v1 v2 pad]: the narrow phase fetches a triangle with three 16-byte loads
         Vf = V_dev if V_dev is not None else torch.from_numpy(np.ascontiguousarray(V, dtype=np.float32)).to(device)
@@ -409,8 +404,7 @@ class FilterPlan:
             bo, bb = getattr(scene, 'blocks_open', None), getattr(scene, 'blocks_bg', None)
             r.open_blocks = bo.data_ptr() if bo is not None and r.n_open_keys else None
             r.bg_blocks = bb.data_ptr() if bb is not None and r.n_bg_keys else None
-        L.lib().cg_filter_segments_prepare.restype = ctypes.c_long
-        E = L.lib().cg_filter_segments_prepare(tab, _c_int(len(segments)))
+        E = L.lib().cg_filter_segments_prepare(tab, len(segments))
         if E < 0:
             raise L.CatgraspAmdError(f'cg_filter_segments_prepare failed with status {E}')
         self.E, self.table, self.n = int(E), tab, len(segments)
@@ -438,7 +432,7 @@ class FilterPlan:
         codes = torch.empty((self.E,), dtype=torch.int8, device=dev)
         if self.E:
             self._wait_upload()
-            check(L.lib().cg_filter_segments_ee_in_base(self.table, _p(self.d_table), _c_int(self.n), _c_int(int(bool(filter_approach_dir_face_camera))),
+            check(L.lib().cg_filter_segments_ee_in_base(self.table, _p(self.d_table), self.n, int(bool(filter_approach_dir_face_camera)),
                                                         _h16(_mat4(cam_in_world, 'cam_in_world')), _h16(_mat4(ee_in_grasp, 'ee_in_grasp')),
                                                         _p(ee), _p(codes), _stream()), 'cg_filter_segments_ee_in_base')
         return ee.view(self.E, 4, 4), codes
@@ -477,10 +471,9 @@ class FilterPlan:
                 ik_ok = torch.from_numpy(ok).to(dev)
         go = ctypes.byref(sc.grid_open.c) if sc.grid_open is not None else None
         ge = ctypes.byref(sc.grid_enc.c) if sc.grid_enc is not None else None
-        head = (self.table, _p(self.d_table), _c_int(self.n), _h16(_mat4(gripper_in_grasp, 'gripper_in_grasp')),
-                _c_int(int(bool(filter_approach_dir_face_camera))))
-        tail = (_p(sc.V), _p(sc.F), _c_int(sc.F.shape[0]), _p(sc.Ve), _p(sc.Fe), _c_int(sc.Fe.shape[0]),
-                ctypes.c_float(sc.res), _p(codes), _p(poses), _p(nudge), go, ge, _c_int(int(bool(keep_rejected_pose))), _p(work_stats), _stream())
+        head = (self.table, _p(self.d_table), self.n, _h16(_mat4(gripper_in_grasp, 'gripper_in_grasp')), int(bool(filter_approach_dir_face_camera)))
+        tail = (_p(sc.V), _p(sc.F), sc.F.shape[0], _p(sc.Ve), _p(sc.Fe), sc.Fe.shape[0],
+                sc.res, _p(codes), _p(poses), _p(nudge), go, ge, int(bool(keep_rejected_pose)), _p(work_stats), _stream())
         if params is not None:
             check(L.lib().cg_filter_grasp_pose_multi_ik(*head, ctypes.byref(params), *tail), 'cg_filter_grasp_pose_multi_ik')
         else:
@@ -524,14 +517,11 @@ def filter_on_device(scene, grasp_poses, symmetry_tfs, nocs_pose, canonical_to_n
     def launch(ik_ok, ee_out):
         go = ctypes.byref(scene.grid_open.c) if scene.grid_open is not None else None
         ge = ctypes.byref(scene.grid_enc.c) if scene.grid_enc is not None else None
-        check(L.lib().cg_filter_grasp_pose_accel(
-            _p(gp), _c_int(n_pose), _p(st), _c_int(n_sym), hm[0], hm[1], hm[2], hm[3], hm[4],
-            _c_int(int(bool(filter_approach_dir_face_camera))), _c_int(int(bool(adjust_collision_pose))), _p(ik_ok),
-            _p(scene.V), _p(scene.F), _c_int(scene.F.shape[0]), _p(scene.Ve), _p(scene.Fe), _c_int(scene.Fe.shape[0]),
-            _p(scene.keys_open), _c_int(scene.keys_open.shape[0]), _p(scene.keys_bg), _c_int(scene.keys_bg.shape[0]),
-            ctypes.c_float(scene.res), _p(codes), _p(poses), _p(nudge), _p(ee_out), go, ge, _c_int(int(bool(keep_rejected_pose))), _p(work_stats),
-            _p(getattr(scene, 'blocks_open', None)), _p(getattr(scene, 'blocks_bg', None)), _stream()),
-              'cg_filter_grasp_pose_accel')
+        check(L.lib().cg_filter_grasp_pose_accel(_p(gp), n_pose, _p(st), n_sym, hm[0], hm[1], hm[2], hm[3], hm[4],
+            int(bool(filter_approach_dir_face_camera)), int(bool(adjust_collision_pose)), _p(ik_ok), _p(scene.V), _p(scene.F), scene.F.shape[0],
+            _p(scene.Ve), _p(scene.Fe), scene.Fe.shape[0], _p(scene.keys_open), scene.keys_open.shape[0], _p(scene.keys_bg), scene.keys_bg.shape[0],
+            scene.res, _p(codes), _p(poses), _p(nudge), _p(ee_out), go, ge, int(bool(keep_rejected_pose)), _p(work_stats), _p(getattr(scene,
+            'blocks_open', None)), _p(getattr(scene, 'blocks_bg', None)), _stream()), 'cg_filter_grasp_pose_accel')
 
     ik_ok = None
     if filter_ik and E > 0:
@@ -616,9 +606,8 @@ def augmentGraspPoses(R0, selected_point, sphere_pts, inplane_rot_step, hand_dep
     sp_d = torch.from_numpy(sp).to(dev)
     F9 = (ctypes.c_float * 9)(*R0.reshape(-1).tolist())
     F3 = (ctypes.c_float * 3)(*p.tolist())
-    check(L.lib().cg_augment_grasp_poses(F9, F3, _p(sp_d), _c_int(len(sp)), _c_int(n_rot), ctypes.c_float(inplane_rot_step), _c_int(n_depth),
-                                         ctypes.c_float(approach_step), ctypes.c_float(init_bite), _p(out), _stream()),
-          'cg_augment_grasp_poses')
+    check(L.lib().cg_augment_grasp_poses(F9, F3, _p(sp_d), len(sp), n_rot, inplane_rot_step, n_depth, approach_step, init_bite,
+                                         _p(out), _stream()), 'cg_augment_grasp_poses')
     poses = out.cpu().numpy().reshape(total, 4, 4)
     return list(poses)
 
@@ -646,9 +635,8 @@ def makeOccupancyGridFromCloudScan(pts, K, resolution, return_tensor=False):
     if nbits > (1 << 33):
         raise MemoryError(f'occupancy bitmap of {nbits} bits is too large; use a coarser resolution')
     bits = torch.zeros(((nbits + 31) // 32,), dtype=torch.int32, device=dev)
-    check(L.lib().cg_occupancy_set_bits(_p(keys), _c_long(keys.shape[0]), _p(bits), _c_int(int(kmin[0])), _c_int(int(kmin[1])),
-                                        _c_int(int(kmin[2])), _c_int(int(dims[0])), _c_int(int(dims[1])), _c_int(int(dims[2])), _stream()),
-          'cg_occupancy_set_bits')
+    check(L.lib().cg_occupancy_set_bits(_p(keys), keys.shape[0], _p(bits), int(kmin[0]), int(kmin[1]), int(kmin[2]), int(dims[0]), int(dims[1]),
+                                        int(dims[2]), _stream()), 'cg_occupancy_set_bits')
     # lattice bounds exactly as common.cpp:353-376 (float32 arithmetic)
     mx = a.max(axis=0); mn = a.min(axis=0)
     pad = np.float32(0.005)
@@ -661,9 +649,7 @@ def makeOccupancyGridFromCloudScan(pts, K, resolution, return_tensor=False):
         return np.zeros((0, 3), dtype=np.float32)
     lattice = torch.empty((total, 3), dtype=torch.float32, device=dev)
     keep = torch.empty((total,), dtype=torch.uint8, device=dev)
-    check(L.lib().cg_occupancy_grid_rays(_p(bits), _c_int(int(kmin[0])), _c_int(int(kmin[1])), _c_int(int(kmin[2])), _c_int(int(dims[0])),
-                                         _c_int(int(dims[1])), _c_int(int(dims[2])), ctypes.c_float(origin[0]), ctypes.c_float(origin[1]),
-                                         ctypes.c_float(origin[2]), ctypes.c_float(res), _c_int(n[0]), _c_int(n[1]), _c_int(n[2]),
-                                         ctypes.c_double(max_range), _p(lattice), _p(keep), _stream()), 'cg_occupancy_grid_rays')
+    check(L.lib().cg_occupancy_grid_rays(_p(bits), int(kmin[0]), int(kmin[1]), int(kmin[2]), int(dims[0]), int(dims[1]), int(dims[2]),
+                                         origin[0], origin[1], origin[2], res, n[0], n[1], n[2], max_range, _p(lattice), _p(keep), _stream()), 'cg_occupancy_grid_rays')
     out = lattice[keep.bool()]
     return out if return_tensor else out.cpu().numpy()

@@ -7,8 +7,6 @@ import torch
 from . import _lib as L
 from ._lib import _p, _stream, check, f32c, i32c, require_cuda
 
-_c_int = ctypes.c_int
-_c_long = ctypes.c_long
 
 # bench.py hook: when set to {'mid_mode': m, 'events': []}, every cg_pointmlp_max launch with that mid_mode is
 # bracketed by HIP events on the launch stream (torch's current stream) so the kernel's average duration can be
@@ -32,9 +30,8 @@ def pointmlp_max(x, w1, b1, w2p, b2, w3p, b3, relu3, t3=None, mid_mode=0, wm=Non
         if timer is not None:
             ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
             ev0.record()
-        args = (_p(x), _c_int(B), _c_int(N), _p(t3), _p(w1), _p(b1), _c_int(mid_mode), _p(wm), _p(bm),
-                _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), _c_int(int(relu3)), _c_int(nsplit),
-                _c_int(tile_points), _p(out), _p(pf))
+        args = (_p(x), B, N, _p(t3), _p(w1), _p(b1), mid_mode, _p(wm), _p(bm),
+                _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), int(relu3), nsplit, tile_points, _p(out), _p(pf))
         if split == 'f16':      # status: caller-owned device int that collects the half range bits (None: not tracked)
             st = L.lib().cg_pointmlp_max_f16x3(*args, _p(status), _stream())
         elif split == 'f16fp8':
@@ -50,9 +47,8 @@ def pointmlp_max(x, w1, b1, w2p, b2, w3p, b3, relu3, t3=None, mid_mode=0, wm=Non
     if timer is not None:
         ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-    st = L.lib().cg_pointmlp_max(_p(x), _c_int(B), _c_int(N), _p(t3), _p(w1), _p(b1), _c_int(mid_mode), _p(wm), _p(bm),
-                                 _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), _c_int(int(relu3)), _c_int(nsplit),
-                                 _p(out), _p(pf), _stream())
+    st = L.lib().cg_pointmlp_max(_p(x), B, N, _p(t3), _p(w1), _p(b1), mid_mode, _p(wm), _p(bm), _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), int(relu3),
+                                 nsplit, _p(out), _p(pf), _stream())
     if timer is not None:
         ev1.record()
         timer['events'].append((ev0, ev1, (B, N)))
@@ -70,9 +66,7 @@ def gemm_bias_act(x, wp, n_out, bias=None, relu=False, eye_k=0, row_bias=None, r
     ld_rb = row_bias.shape[1] if row_bias is not None else 0
     name = {'f16': 'cg_gemm_bias_act_f16x3', 'bf16': 'cg_gemm_bias_act_bf16x3'}.get(split, 'cg_gemm_bias_act')
     fn = getattr(L.lib(), name)
-    args = (_p(x), _c_int(M), _c_int(K), _c_int(K), _p(wp), _c_int(n_out), _p(bias),
-            _p(row_bias), _c_int(rows_per_group), _c_int(ld_rb), _c_int(int(relu)),
-            _c_int(eye_k), _p(y), _c_int(n_out))
+    args = (_p(x), M, K, K, _p(wp), n_out, _p(bias), _p(row_bias), rows_per_group, ld_rb, int(relu), eye_k, _p(y), n_out)
     st = fn(*args, _p(status), _stream()) if split == 'f16' else fn(*args, _stream())
     check(st, name)
     return y
@@ -85,7 +79,7 @@ def group_max(x, groups):
     rows = x.shape[0] // max(groups, 1)
     assert groups * rows == x.shape[0]
     out = torch.empty((groups, x.shape[1]), dtype=torch.float32, device=x.device)
-    check(L.lib().cg_group_max(_p(x), _c_long(groups), _c_long(rows), _c_int(x.shape[1]), _p(out), _stream()), 'cg_group_max')
+    check(L.lib().cg_group_max(_p(x), groups, rows, x.shape[1], _p(out), _stream()), 'cg_group_max')
     return out
 
 
@@ -98,7 +92,7 @@ def pose_inverse_rows_f64(poses, center, bad=None):
     assert poses.dtype == torch.float64 and poses.is_contiguous() and poses.shape[1] == 16
     out = torch.empty((poses.shape[0], 12), dtype=torch.float32, device=poses.device)
     c = (ctypes.c_double * 3)(*[float(v) for v in center])
-    check(L.lib().cg_pose_inverse_rows_f64(_p(poses), _c_long(poses.shape[0]), c, _p(out), _p(bad), _stream()), 'cg_pose_inverse_rows_f64')
+    check(L.lib().cg_pose_inverse_rows_f64(_p(poses), poses.shape[0], c, _p(out), _p(bad), _stream()), 'cg_pose_inverse_rows_f64')
     return out
 
 
@@ -122,8 +116,7 @@ def softmax_pg(logits):
     label = torch.empty((B,), dtype=torch.int32, device=logits.device)
     conf = torch.empty((B,), dtype=torch.float32, device=logits.device)
     pg = torch.empty((B,), dtype=torch.float32, device=logits.device)
-    check(L.lib().cg_softmax_pg(_p(logits), _c_int(B), _c_int(C), _p(probs), _p(label), _p(conf), _p(pg), _stream()),
-          'cg_softmax_pg')
+    check(L.lib().cg_softmax_pg(_p(logits), B, C, _p(probs), _p(label), _p(conf), _p(pg), _stream()), 'cg_softmax_pg')
     return probs, label, conf, pg
 
 
@@ -136,8 +129,7 @@ def apply_shuffle_rows(partners, n_valid, n_pts, base=0, out=None):
     count, stride = partners.shape
     if out is None:
         out = torch.empty((count, n_pts), dtype=torch.int32, device=partners.device)
-    check(L.lib().cg_apply_shuffle_rows(_p(partners), _c_long(stride), _c_int(n_valid), _c_int(n_pts), _c_long(count), _c_int(base), _p(out),
-                                        _stream()), 'cg_apply_shuffle_rows')
+    check(L.lib().cg_apply_shuffle_rows(_p(partners), stride, n_valid, n_pts, count, base, _p(out), _stream()), 'cg_apply_shuffle_rows')
     return out
 
 
@@ -149,8 +141,7 @@ def nunocs_decode(logits, nbins):
     assert logits.shape[1] == 3 * nbins
     coords = torch.empty((P, 3), dtype=torch.float32, device=logits.device)
     conf = torch.empty((P,), dtype=torch.float32, device=logits.device)
-    check(L.lib().cg_nunocs_decode(_p(logits), _c_long(P), _c_int(nbins), _p(coords), _p(conf), _stream()),
-          'cg_nunocs_decode')
+    check(L.lib().cg_nunocs_decode(_p(logits), P, nbins, _p(coords), _p(conf), _stream()), 'cg_nunocs_decode')
     return coords, conf
 
 
@@ -166,8 +157,8 @@ def build_grasp_input(cloud_xyz, cloud_normal, ids, pose_inv, mean=None, inv_std
     if timer is not None:
         ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-    st = L.lib().cg_build_grasp_input(_p(cloud_xyz), _p(cloud_normal), _c_int(cloud_xyz.shape[0]), _p(ids), _p(pose_inv),
-                                      _p(mean), _p(inv_std), _c_int(G), _c_int(n_pts), _p(out), _stream())
+    st = L.lib().cg_build_grasp_input(_p(cloud_xyz), _p(cloud_normal), cloud_xyz.shape[0], _p(ids), _p(pose_inv),
+                                      _p(mean), _p(inv_std), G, n_pts, _p(out), _stream())
     if timer is not None:
         ev1.record()
         timer['bgi_events'].append((ev0, ev1, G))
@@ -181,7 +172,6 @@ def build_nunocs_input(cloud_xyz, cloud_normal, ids, mean=None, inv_std=None):
     f32c(cloud_xyz); f32c(cloud_normal); i32c(ids)
     B, n_pts = ids.shape
     out = torch.empty((B, n_pts, 6), dtype=torch.float32, device=ids.device)
-    check(L.lib().cg_build_nunocs_input(_p(cloud_xyz), _p(cloud_normal), _c_int(cloud_xyz.shape[0]), _p(ids),
-                                        _p(mean), _p(inv_std), _c_int(B), _c_int(n_pts), _p(out), _stream()),
-          'cg_build_nunocs_input')
+    check(L.lib().cg_build_nunocs_input(_p(cloud_xyz), _p(cloud_normal), cloud_xyz.shape[0], _p(ids), _p(mean), _p(inv_std), B, n_pts, _p(out),
+                                        _stream()), 'cg_build_nunocs_input')
     return out

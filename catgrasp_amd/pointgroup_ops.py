@@ -1,14 +1,11 @@
 """Row N4: forward passes of the reference's `pointgroup_ops` CUDA extension
 (PointGroup/lib/pointgroup_ops/functions/pointgroup_ops.py) used on the inference path (predicter.py:285-304), on HIP.
 Same function names and tensor conventions (int32 index tensors, CSR offsets)."""
-import ctypes
 
 import torch
 
 from . import _lib as L
 from ._lib import _p, _stream, check, require_cuda
-
-_c_int = ctypes.c_int
 
 
 def _on_device(*tensors):
@@ -37,7 +34,7 @@ def ballquery_batch_p(coords, batch_idxs, batch_offsets, radius, meanActive):
     n = coords.shape[0]
     counts = torch.zeros((n,), dtype=torch.int32, device=coords.device)
     lib = L.lib()
-    check(lib.cg_pg_ballquery_batch_p(_p(coords), _p(batch_idxs), _p(batch_offsets), _c_int(n), ctypes.c_float(radius), _c_int(0), None, None,
+    check(lib.cg_pg_ballquery_batch_p(_p(coords), _p(batch_idxs), _p(batch_offsets), n, radius, 0, None, None,
                                       _p(counts), None, _stream()), 'cg_pg_ballquery_batch_p')
     csum = torch.cumsum(counts.long(), 0)
     total = int(csum[-1].item()) if n else 0
@@ -45,7 +42,7 @@ def ballquery_batch_p(coords, batch_idxs, batch_offsets, radius, meanActive):
         raise ValueError('ballquery_batch_p: more than 2^31 neighbour entries')
     start = (csum - counts).int().contiguous()
     idx = torch.zeros((max(total, 1),), dtype=torch.int32, device=coords.device)
-    check(lib.cg_pg_ballquery_batch_p(_p(coords), _p(batch_idxs), _p(batch_offsets), _c_int(n), ctypes.c_float(radius), _c_int(1), _p(start),
+    check(lib.cg_pg_ballquery_batch_p(_p(coords), _p(batch_idxs), _p(batch_offsets), n, radius, 1, _p(start),
                                       _p(counts), None, _p(idx), _stream()), 'cg_pg_ballquery_batch_p')
     start_len = torch.stack([start, counts], dim=1).contiguous()
     return idx[:total].contiguous(), start_len
@@ -58,8 +55,7 @@ def _segment(inp, offsets, mode, want_argmax=False):
     C = inp.shape[1]
     out = torch.zeros((nseg, C), dtype=torch.float32, device=inp.device)
     am = torch.zeros((nseg, C), dtype=torch.int32, device=inp.device) if want_argmax else None
-    check(L.lib().cg_pg_segment_reduce(_p(inp), _p(offsets), _c_int(nseg), _c_int(C), _c_int(mode), _p(out), _p(am), _stream()),
-          'cg_pg_segment_reduce')
+    check(L.lib().cg_pg_segment_reduce(_p(inp), _p(offsets), nseg, C, mode, _p(out), _p(am), _stream()), 'cg_pg_segment_reduce')
     return (out, am) if want_argmax else out
 
 
@@ -85,7 +81,7 @@ def get_iou(proposals_idx, proposals_offset, instance_labels, instance_pointnum)
     nI = instance_pointnum.shape[0]; nP = proposals_offset.shape[0] - 1
     iou = torch.zeros((nP, nI), dtype=torch.float32, device=proposals_idx.device)
     check(L.lib().cg_pg_get_iou(_p(proposals_idx.contiguous().int()), _p(proposals_offset.contiguous().int()), _p(instance_labels.contiguous().long()),
-                                _p(instance_pointnum.contiguous().int()), _c_int(nP), _c_int(nI), _p(iou), _stream()), 'cg_pg_get_iou')
+                                _p(instance_pointnum.contiguous().int()), nP, nI, _p(iou), _stream()), 'cg_pg_get_iou')
     return iou
 
 
@@ -96,8 +92,7 @@ def voxelization(feats, map_rule, mode=4):
     M, width = rules.shape
     C = feats.shape[1]
     out = torch.zeros((M, C), dtype=torch.float32, device=feats.device)
-    check(L.lib().cg_pg_voxelize_fp(_p(feats), _p(rules), _c_int(M), _c_int(width - 1), _c_int(C), _c_int(int(mode == 4)), _p(out), _stream()),
-          'cg_pg_voxelize_fp')
+    check(L.lib().cg_pg_voxelize_fp(_p(feats), _p(rules), M, width - 1, C, int(mode == 4), _p(out), _stream()), 'cg_pg_voxelize_fp')
     return out
 
 
@@ -113,8 +108,7 @@ def point_recover(feats, map_rule, nPoint):
     C = feats.shape[1]
     out = torch.zeros((int(nPoint), C), dtype=torch.float32, device=feats.device)
     err = torch.zeros((1,), dtype=torch.int32, device=feats.device)
-    check(L.lib().cg_pg_point_recover(_p(feats), _p(rules), _c_int(M), _c_int(width - 1), _c_int(C), _c_int(int(nPoint)), _p(out), _p(err),
-                                      _stream()), 'cg_pg_point_recover')
+    check(L.lib().cg_pg_point_recover(_p(feats), _p(rules), M, width - 1, C, int(nPoint), _p(out), _p(err), _stream()), 'cg_pg_point_recover')
     if int(err.item()):
         raise ValueError('point_recover: a rule lists more members than maxActive or a point outside [0, nPoint)')
     return out
@@ -138,10 +132,10 @@ def voxelization_idx(coords, batchsize, mode=4):
     lib = L.lib()
     keys = torch.empty((n,), dtype=torch.int64, device=dev)
     err = torch.zeros((1,), dtype=torch.int32, device=dev)
-    check(lib.cg_pg_voxel_pack_keys(_p(coords), _c_int(n), _c_int(ncol), _p(keys), _p(err), _stream()), 'cg_pg_voxel_pack_keys')
+    check(lib.cg_pg_voxel_pack_keys(_p(coords), n, ncol, _p(keys), _p(err), _stream()), 'cg_pg_voxel_pack_keys')
     skeys, perm = torch.sort(keys, stable=True)                         # ties keep point order
     head = torch.empty((n,), dtype=torch.int32, device=dev)
-    check(lib.cg_pg_segment_heads(_p(skeys), _c_int(n), _p(head), _stream()), 'cg_pg_segment_heads')
+    check(lib.cg_pg_segment_heads(_p(skeys), n, _p(head), _stream()), 'cg_pg_segment_heads')
     seg = (torch.cumsum(head, 0) - 1).int()
     seg_start = torch.nonzero(head, as_tuple=False).reshape(-1).int()  # also: its length M and the sync point
     if int(err.item()):
@@ -160,7 +154,7 @@ def voxelization_idx(coords, batchsize, mode=4):
             raise ValueError('voxelization_idx mode 0 needs unique coordinates')
     input_map = torch.empty((n,), dtype=torch.int32, device=dev)
     output_map = torch.zeros((M, max_active + 1), dtype=torch.int32, device=dev)
-    check(lib.cg_pg_voxel_fill_maps(_p(perm), _p(seg), _p(seg_start), _p(vid), _c_int(n), _c_int(max_active + 1), _c_int(int(mode)),
+    check(lib.cg_pg_voxel_fill_maps(_p(perm), _p(seg), _p(seg_start), _p(vid), n, max_active + 1, int(mode),
                                     _p(input_map), _p(output_map), _stream()), 'cg_pg_voxel_fill_maps')
     output_coords = coords[output_map[:, 1].long()]                     # voxelize_outputmap: coords of rule[1]
     return output_coords, input_map, output_map
@@ -196,7 +190,7 @@ def bfs_cluster(semantic_label, ball_query_idxs, start_len, threshold):
     for _ in range(max(n, 1) + 1):
         changed.zero_()
         for _ in range(4):                                              # a few sweeps per host round trip
-            check(lib.cg_pg_cc_propagate(_p(label), _p(nbr), _c_int(n_idx), _p(sl), _c_int(n), _p(comp), _p(changed), _stream()), 'cg_pg_cc_propagate')
+            check(lib.cg_pg_cc_propagate(_p(label), _p(nbr), n_idx, _p(sl), n, _p(comp), _p(changed), _stream()), 'cg_pg_cc_propagate')
         if int(changed.item()) == 0:
             break
     sizes = torch.bincount(comp.long(), minlength=n)

@@ -7,9 +7,6 @@ import torch
 from . import _lib as L
 from ._lib import _p, _stream, check, require_cuda
 
-_c_int = ctypes.c_int
-_c_long = ctypes.c_long
-
 
 def _f32(t):
     return t.contiguous().float()
@@ -25,7 +22,7 @@ def square_distance(src, dst):
     if dst.shape[0] != B or dst.shape[2] != C or C < 1:
         raise ValueError(f'square_distance: src {tuple(src.shape)} and dst {tuple(dst.shape)} do not match')
     out = torch.empty((B, N, M), dtype=torch.float32, device=src.device)
-    check(L.lib().cg_square_distance_nd(_p(src), _p(dst), _c_int(B), _c_int(N), _c_int(M), _c_int(C), _p(out), _stream()), 'cg_square_distance_nd')
+    check(L.lib().cg_square_distance_nd(_p(src), _p(dst), B, N, M, C, _p(out), _stream()), 'cg_square_distance_nd')
     return out
 
 
@@ -43,8 +40,7 @@ def index_points(points, idx):
     S = idx[0].numel() if B > 0 else 0
     out = torch.empty(tuple(idx.shape) + (C,), dtype=torch.float32, device=points.device)
     err = torch.zeros((1,), dtype=torch.int32, device=points.device)
-    check(L.lib().cg_index_points(_p(points), _p(idx), _c_int(B), _c_int(N), _c_int(C), _c_long(S), _p(out), _p(err), _stream()),
-          'cg_index_points')
+    check(L.lib().cg_index_points(_p(points), _p(idx), B, N, C, S, _p(out), _p(err), _stream()), 'cg_index_points')
     _raise_if(err, 'index_points')
     return out
 
@@ -78,11 +74,10 @@ def farthest_point_sample(xyz, npoint, start=None, return_xyz=False, start_prepa
     scratch = torch.empty((B, N), dtype=torch.float32, device=xyz.device) if N > 24576 else None
     if return_xyz:
         new_xyz = torch.empty((B, npoint, 3), dtype=torch.float32, device=xyz.device)
-        check(L.lib().cg_farthest_point_sample_xyz(_p(xyz), _p(start), _c_int(B), _c_int(N), _c_int(npoint), _p(scratch), _p(out), _p(new_xyz),
+        check(L.lib().cg_farthest_point_sample_xyz(_p(xyz), _p(start), B, N, npoint, _p(scratch), _p(out), _p(new_xyz),
                                                    _stream()), 'cg_farthest_point_sample_xyz')
         return out, new_xyz
-    check(L.lib().cg_farthest_point_sample(_p(xyz), _p(start), _c_int(B), _c_int(N), _c_int(npoint), _p(scratch), _p(out), _stream()),
-          'cg_farthest_point_sample')
+    check(L.lib().cg_farthest_point_sample(_p(xyz), _p(start), B, N, npoint, _p(scratch), _p(out), _stream()), 'cg_farthest_point_sample')
     return out
 
 
@@ -97,8 +92,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     ns = min(int(nsample), N)
     out = torch.empty((B, S, ns), dtype=torch.int64, device=xyz.device)
     r2 = float(torch.tensor(radius ** 2, dtype=torch.float32))     # the comparison is made in float32
-    check(L.lib().cg_query_ball_point(_p(xyz), _p(new_xyz), _c_int(B), _c_int(N), _c_int(S), ctypes.c_float(r2), _c_int(ns), _p(out),
-                                      _stream()), 'cg_query_ball_point')
+    check(L.lib().cg_query_ball_point(_p(xyz), _p(new_xyz), B, N, S, r2, ns, _p(out), _stream()), 'cg_query_ball_point')
     return out
 
 
@@ -118,7 +112,7 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     new_points = torch.empty((B, S, K, 3 + D), dtype=torch.float32, device=xyz.device)
     grouped_xyz = torch.empty((B, S, K, 3), dtype=torch.float32, device=xyz.device) if returnfps else None
     err = torch.zeros((1,), dtype=torch.int32, device=xyz.device)
-    check(L.lib().cg_group_points(_p(xyz), _p(points), _p(new_xyz), _p(idx), _c_int(B), _c_int(N), _c_int(S), _c_int(K), _c_int(D),
+    check(L.lib().cg_group_points(_p(xyz), _p(points), _p(new_xyz), _p(idx), B, N, S, K, D,
                                   _p(new_points), _p(grouped_xyz), _p(err), _stream()), 'cg_group_points')
     _raise_if(err, 'sample_and_group (a query ball was empty)')
     if returnfps:
@@ -224,15 +218,13 @@ def group_mlp_max(xyz, points, new_xyz, idx, W, check_indices=True, channels_las
     if append_xyz and (W.kind != 'tile' or not channels_last or cs != 1):
         raise ValueError("append_xyz needs kind='tile' weights and a channels_last output with unit channel stride")
     if W.kind == 'reg':
-        check(L.lib().cg_sa_group_mlp_max_strided(_p(xyz), _p(points), _p(new_xyz), _p(idx), _c_int(B), _c_int(N), _c_int(S), _c_int(K), _c_int(D),
-                                                  _c_int(L_), cin, cout, wp, bp, _p(out), _c_long(sb), _c_long(ss), _c_long(cs), _p(err),
-                                                  _stream()), 'cg_sa_group_mlp_max_strided')
+        check(L.lib().cg_sa_group_mlp_max_strided(_p(xyz), _p(points), _p(new_xyz), _p(idx), B, N, S, K, D, L_, cin, cout, wp, bp, _p(out), sb, ss,
+                                                  cs, _p(err), _stream()), 'cg_sa_group_mlp_max_strided')
     else:
         if W.cin[0] > W.TILE_MAX_CIN or W.hidden_max > 512:
             raise NotImplementedError('fused set abstraction (tile kernel): 3 + D <= 592 inputs, hidden widths <= 512')
-        check(L.lib().cg_sa_tile_mlp_max(_p(xyz), _p(points), _p(new_xyz), _p(idx), _c_int(B), _c_int(N), _c_int(S), _c_int(K), _c_int(D),
-                                         _c_int(L_), cin, cout, wp, bp, _p(out), _c_long(sb), _c_long(ss), _c_long(cs), _c_int(int(append_xyz)), _p(err),
-                                         _stream()), 'cg_sa_tile_mlp_max')
+        check(L.lib().cg_sa_tile_mlp_max(_p(xyz), _p(points), _p(new_xyz), _p(idx), B, N, S, K, D, L_, cin, cout, wp, bp, _p(out), sb, ss, cs,
+                                         int(append_xyz), _p(err), _stream()), 'cg_sa_tile_mlp_max')
     if not check_indices:
         return out, err
     _raise_if(err, 'group_mlp_max (a query ball was empty or an index is out of range)')
@@ -267,9 +259,8 @@ def group_all_mlp_max(xyz, points, W, fused=False, rows=None):
             raise NotImplementedError('fused group-all layer: 3 + D <= 592 inputs, hidden widths <= 512')
         out = torch.empty((B, C), dtype=torch.float32, device=xyz.device)
         L_, cin, cout, wp, bp = W._c_arrays()
-        check(L.lib().cg_sa_tile_mlp_max(_p(xyz), _p(points), _p(None), _p(None), _c_int(B), _c_int(N), _c_int(1), _c_int(N), _c_int(D),
-                                         _c_int(L_), cin, cout, wp, bp, _p(out), _c_long(C), _c_long(0), _c_long(1), _c_int(0), _p(None), _stream()),
-              'cg_sa_tile_mlp_max')
+        check(L.lib().cg_sa_tile_mlp_max(_p(xyz), _p(points), _p(None), _p(None), B, N, 1, N, D, L_, cin, cout, wp, bp, _p(out), C, 0, 1, 0, _p(None),
+                                         _stream()), 'cg_sa_tile_mlp_max')
         return out
     if rows is not None:       # the previous level already wrote the [features | xyz | pad] rows (group_mlp_max(append_xyz=...))
         if tuple(rows.shape) != (B * N, W.cin[0]) or not rows.is_contiguous() or rows.dtype != torch.float32:
@@ -277,10 +268,10 @@ def group_all_mlp_max(xyz, points, W, fused=False, rows=None):
         h = rows
     else:
         h = torch.empty((B * N, W.cin[0]), dtype=torch.float32, device=xyz.device)
-        check(L.lib().cg_sa_concat_input(_p(xyz), _p(points), _c_long(B * N), _c_int(D), _c_int(W.cin[0]), _p(h), _stream()), 'cg_sa_concat_input')
+        check(L.lib().cg_sa_concat_input(_p(xyz), _p(points), B * N, D, W.cin[0], _p(h), _stream()), 'cg_sa_concat_input')
     for wp, b, co in zip(W.w[:-1], W.b[:-1], W.cout[:-1]):
         h = ops.gemm_bias_act(h, wp, co, bias=b, relu=True)
     out = torch.empty((B, C), dtype=torch.float32, device=xyz.device)       # last layer: the max over the N points in the GEMM's epilogue
-    check(L.lib().cg_gemm_bias_relu_groupmax(_p(h), _c_int(B * N), _c_int(h.shape[1]), _c_int(h.shape[1]), _p(W.w[-1]), _c_int(C), _p(W.b[-1]),
-                                             _c_int(N), _p(out), _stream()), 'cg_gemm_bias_relu_groupmax')
+    check(L.lib().cg_gemm_bias_relu_groupmax(_p(h), B * N, h.shape[1], h.shape[1], _p(W.w[-1]), C, _p(W.b[-1]),
+                                             N, _p(out), _stream()), 'cg_gemm_bias_relu_groupmax')
     return out

@@ -2,16 +2,12 @@
 meshpy/meshpy/sdf_file.py:59-87) for the lookups the grasp path prepares: grid<->object transform,
 trilinear / nearest signed distance, any-point-inside, and the batched per-candidate form.
 Lookups run in csrc/sdf.hip; there is no CPU fallback."""
-import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from ._lib import _p, _stream, check
-
-_c_int = ctypes.c_int
-_c_long = ctypes.c_long
 
 
 class Sdf3D:
@@ -65,8 +61,7 @@ class Sdf3D:
         B, _, N = t.shape
         out = torch.empty((B, N), dtype=torch.float32, device=self.device)
         nx, ny, nz = (int(v) for v in self.dims_)
-        check(L.lib().cg_sdf_lookup(_p(self.data_torch), _c_int(nx), _c_int(ny), _c_int(nz), _p(t), _c_long(B), _c_long(N),
-                                    _c_int(mode), _p(out), _stream()), 'cg_sdf_lookup')
+        check(L.lib().cg_sdf_lookup(_p(self.data_torch), nx, ny, nz, _p(t), B, N, mode, _p(out), _stream()), 'cg_sdf_lookup')
         return out
 
     def _signed_distance(self, coords, fast=False):
@@ -85,8 +80,7 @@ class Sdf3D:
         assert t.shape[0] == 1
         flag = torch.zeros((1,), dtype=torch.int32, device=self.device)
         nx, ny, nz = (int(v) for v in self.dims_)
-        check(L.lib().cg_sdf_any_inside(_p(self.data_torch), _c_int(nx), _c_int(ny), _c_int(nz), _p(t), _c_long(t.shape[2]), _p(flag),
-                                        _stream()), 'cg_sdf_any_inside')
+        check(L.lib().cg_sdf_any_inside(_p(self.data_torch), nx, ny, nz, _p(t), t.shape[2], _p(flag), _stream()), 'cg_sdf_any_inside')
         return bool(flag.item())
 
     def is_any_points_inside_batch(self, sdf_in_cam, pts_cam):
@@ -100,8 +94,8 @@ class Sdf3D:
         pts = pts.to(device=self.device, dtype=torch.float32).contiguous()
         out = torch.zeros((E,), dtype=torch.uint8, device=self.device)
         nx, ny, nz = (int(v) for v in self.dims_)
-        check(L.lib().cg_sdf_points_inside_batch(_p(self.data_torch), _c_int(nx), _c_int(ny), _c_int(nz), _p(xf_d), _c_long(E), _p(pts),
-                                                 _c_int(pts.shape[0]), _p(out), _stream()), 'cg_sdf_points_inside_batch')
+        check(L.lib().cg_sdf_points_inside_batch(_p(self.data_torch), nx, ny, nz, _p(xf_d), E, _p(pts), pts.shape[0],
+                                                 _p(out), _stream()), 'cg_sdf_points_inside_batch')
         return out.bool()
 
 

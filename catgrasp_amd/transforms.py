@@ -46,13 +46,13 @@ class NumpyChoiceStream:
         assert out.shape == (count, self.n_pts) and out.dtype == np.int32 and out.flags.c_contiguous
         if self.on_device_chain:         # replace=False, n_valid <= 65536: vectorised partner extraction + the swap chain in L1
             from . import _lib as L
-            rc = L.lib().cg_host_numpy_permutation_rows(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), ct.c_int(self.n_valid),
-                                                        ct.c_int(self.n_pts), ct.c_long(count), ct.c_int(0), out.ctypes.data_as(ct.c_void_p))
+            rc = L.lib().cg_host_numpy_permutation_rows(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), self.n_valid,
+                                                        self.n_pts, count, 0, out.ctypes.data_as(ct.c_void_p))
             if rc != 0:
                 raise RuntimeError(f'cg_host_numpy_permutation_rows failed with status {rc}')
             return out
-        rc = self._fn(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), ct.c_int(self.n_valid), ct.c_int(self.n_pts),
-                      ct.c_long(count), self._scratch.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p))
+        rc = self._fn(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), self.n_valid, self.n_pts,
+                      count, self._scratch.ctypes.data_as(ct.c_void_p), out.ctypes.data_as(ct.c_void_p))
         if rc != 0:
             raise RuntimeError(f'cg_host_numpy_choice_rows failed with status {rc}')
         return out
@@ -77,8 +77,8 @@ class NumpyChoiceStream:
         if out is None:
             out = np.empty((count, stride), dtype=np.uint16)
         assert out.shape == (count, stride) and out.dtype == np.uint16 and out.flags.c_contiguous
-        rc = L.lib().cg_host_numpy_shuffle_partners(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), ct.c_int(self.n_valid),
-                                                    ct.c_long(count), ct.c_long(stride), out.ctypes.data_as(ct.c_void_p))
+        rc = L.lib().cg_host_numpy_shuffle_partners(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), self.n_valid,
+                                                    count, stride, out.ctypes.data_as(ct.c_void_p))
         if rc != 0:
             raise RuntimeError(f'cg_host_numpy_shuffle_partners failed with status {rc}')
         return out
@@ -114,8 +114,7 @@ class NumpyHeadsDraw:
         def run():
             import time
             t0 = time.perf_counter()
-            rc = fn(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), ct.c_int(n), ct.c_int(k), ct.c_long(count),
-                    ct.c_int(isa), self._out.ctypes.data_as(ct.c_void_p))
+            rc = fn(self._key.ctypes.data_as(ct.c_void_p), ct.byref(self._pos), n, k, count, isa, self._out.ctypes.data_as(ct.c_void_p))
             self.seconds = time.perf_counter() - t0
             if rc != 0:
                 raise RuntimeError(f'cg_host_numpy_choice_heads failed with status {rc}')
@@ -190,7 +189,6 @@ def draw_ids_device(n_valid, n_pts, count, device, generator=None, seed=None, ba
     (= replace=True).  Counter-based: `seed` (or the next draw of `generator`, or a process-wide counter seeded from numpy's
     global generator) and the global row index `row_offset + r` fix every row, so a shard of a batch draws what the whole batch
     would.  -> (count, n_pts) int32 cuda tensor, each id offset by `base`."""
-    import ctypes
     from . import _lib as L
     if seed is None:
         if generator is not None:
@@ -203,8 +201,7 @@ def draw_ids_device(n_valid, n_pts, count, device, generator=None, seed=None, ba
     if out is None:
         out = torch.empty((count, n_pts), dtype=torch.int32, device=device)
     assert out.shape == (count, n_pts) and out.dtype == torch.int32 and out.is_contiguous() and out.is_cuda
-    st = L.lib().cg_draw_resample_ids(ctypes.c_int(n_valid), ctypes.c_int(n_pts), ctypes.c_long(count), ctypes.c_ulonglong(seed & (2 ** 64 - 1)),
-                                      ctypes.c_int(base), ctypes.c_long(row_offset), L._p(out), L._stream())
+    st = L.lib().cg_draw_resample_ids(n_valid, n_pts, count, seed & (2 ** 64 - 1), base, row_offset, L._p(out), L._stream())
     if st == -2:        # CG_ERR_UNSUPPORTED: a shape outside the kernel's (without replacement from > 65535 points; n_pts % 4 != 0)
         gen = torch.Generator(device=device); gen.manual_seed((seed + 0x9E3779B97F4A7C15 * (row_offset + 1)) % (2 ** 63))
         if n_valid < n_pts:
@@ -225,7 +222,7 @@ def pose_inverse_rows_device(poses, center):
     assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
     out = torch.empty((p.shape[0], 12), dtype=torch.float32, device=p.device)
     c = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(center, dtype=np.float64).reshape(3)])
-    L.check(L.lib().cg_pose_inverse_rows(L._p(p), ctypes.c_long(p.shape[0]), c, L._p(out), L._stream()), 'cg_pose_inverse_rows')
+    L.check(L.lib().cg_pose_inverse_rows(L._p(p), p.shape[0], c, L._p(out), L._stream()), 'cg_pose_inverse_rows')
     return out
 
 

@@ -44,6 +44,110 @@ def test_header_is_plain_c_and_links_from_c(tmp_path):
     assert 'gfx950' in out.stdout and out.stdout.split()[-1] == str(len(syms))
 
 
+def test_struct_mirrors_match_the_header_layout(tmp_path):
+    """The four ctypes.Structure mirrors of header structs have the header's size and field offsets: a C program prints sizeof and
+    every field's offsetof (field names from the mirrors' _fields_, which use the header's names), compared with ctypes.  A mirror
+    that lacks a header field fails on sizeof, a misordered one on an offset, a misnamed one at compile time."""
+    import shutil
+    import subprocess
+    from catgrasp_amd import engine, my_cpp
+    if shutil.which('gcc') is None:
+        pytest.skip('gcc not available')
+    mirrors = {'cg_cls_weights': engine._ClsWeightsC, 'cg_mesh_grid': my_cpp._MeshGridC, 'cg_filter_segment': my_cpp._FilterSegmentC,
+               'cg_iiwa_ik_params': my_cpp._IkParamsC}
+    src = '#include "catgrasp_amd.h"\n#include <stdio.h>\nint main(void) {\n'
+    for name, cls in mirrors.items():
+        src += f'  printf("{name} %d\\n", (int)sizeof({name}));\n'
+        src += ''.join(f'  printf("{name}.{f} %d\\n", (int)offsetof({name}, {f}));\n' for f, *_ in cls._fields_)
+    (tmp_path / 'layout.c').write_text(src + '  return 0;\n}\n')
+    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.dirname(_lib.HEADER_PATH), 'layout.c',
+                           '-o', 'layout'], cwd=tmp_path)
+    out = subprocess.run([str(tmp_path / 'layout')], capture_output=True, text=True, check=True).stdout
+    got = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    want = {}
+    for name, cls in mirrors.items():
+        want[name] = ctypes.sizeof(cls)
+        want.update({f'{name}.{f}': getattr(cls, f).offset for f, *_ in cls._fields_})
+    assert got == want
+
+
+def _header_prototypes():
+    """{name: (return type text, [parameter texts])} read from the header independently of _lib.signatures: comments stripped, then
+    one search per declared name."""
+    import re
+    with open(_lib.HEADER_PATH) as f:
+        text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    protos = {}
+    for name in _lib.declared_symbols():
+        m = re.search(r'([A-Za-z_][A-Za-z_ ]*\*?)\s+' + name + r'\s*\(([^)]*)\)\s*;', text)
+        params = [] if m.group(2).strip() == 'void' else [' '.join(q.split()) for q in m.group(2).split(',')]
+        protos[name] = (m.group(1).strip(), params)
+    return protos
+
+
+def test_every_entry_point_is_bound_with_the_header_types():
+    """lib() sets argtypes and restype of EVERY declared function from the header: one argtype per parameter, pointers as c_void_p,
+    scalars by the fixed mapping; a few prototypes spelled out literally."""
+    lib = _lib.lib()
+    vp, ci, cl, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+    scalars = {'int': ci, 'long': cl, 'float': cf, 'double': cd, 'unsigned long long': ctypes.c_ulonglong, 'size_t': ctypes.c_size_t}
+    protos = _header_prototypes()
+    assert len(protos) == len(_lib.declared_symbols()) == 71
+    for name, (ret, params) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        for at, q in zip(fn.argtypes, params):
+            assert at is (vp if '*' in q else scalars[q.rsplit(' ', 1)[0]]), (name, q)
+        assert fn.restype is (ctypes.c_char_p if ret == 'const char*' else scalars[ret]), name
+    assert tuple(lib.cg_group_max.argtypes) == (vp, cl, cl, ci, vp, vp)
+    assert tuple(lib.cg_voxels_voxels_collide.argtypes) == (vp, ci, cf, vp, ci, cf, vp, vp, vp)
+    assert tuple(lib.cg_draw_resample_ids.argtypes) == (ci, ci, cl, ctypes.c_ulonglong, ci, cl, vp, vp)
+    assert tuple(lib.cg_mesh_grid_count.argtypes) == (vp, vp, ci, vp, cd, cd, vp, vp, vp)
+    assert lib.cg_filter_segments_prepare.restype is cl and tuple(lib.cg_filter_segments_prepare.argtypes) == (vp, ci)
+    assert lib.cg_pointnet_cls_workspace_floats.restype is ctypes.c_size_t and tuple(lib.cg_pointnet_cls_workspace_floats.argtypes) == (ci,)
+    assert lib.cg_version.restype is ctypes.c_char_p and tuple(lib.cg_version.argtypes) == ()
+    assert lib.cg_gemm_bias_act.restype is ci
+
+
+def test_calls_that_do_not_match_the_prototype_never_reach_c():
+    """With argtypes set ctypes refuses a call before it is made: a missing argument, a float for an int, a list for a pointer, a ctypes
+    scalar of another type than declared.  (Every call below would be an argument error -- null x -- if it did reach the library.)"""
+    lib = _lib.lib()
+    null, one = ctypes.c_void_p(0), ctypes.c_void_p(16)
+    assert lib.cg_group_max(null, 4, 4, 8, one, null) == -1                    # well-formed: reaches C, which reports the null x
+    with pytest.raises(TypeError):
+        lib.cg_group_max(null, 4, 4, 8, one)                                   # one argument missing
+    with pytest.raises(ctypes.ArgumentError):
+        lib.cg_group_max(null, 4, 4, 8.0, one, null)                           # float for int
+    with pytest.raises(ctypes.ArgumentError):
+        lib.cg_group_max([0], 4, 4, 8, one, null)                              # list for a pointer
+    with pytest.raises(ctypes.ArgumentError):
+        lib.cg_group_max(null, 4, 4, ctypes.c_long(8), one, null)              # c_long instance for int
+    with pytest.raises(ctypes.ArgumentError):
+        lib.cg_voxel_keys(one, 5, ctypes.c_double(0.001), one, null)           # c_double instance for float
+    with pytest.raises(ctypes.ArgumentError):
+        lib.cg_group_max(ctypes.c_int(0), 4, 4, 8, one, null)                  # c_int instance for a pointer
+    # a count past 2**31 for a `long` parameter arrives intact (a null x still comes back as the argument error, not a truncated count)
+    assert lib.cg_group_max(null, 2 ** 31 + 5, 4, 8, one, null) == -1
+
+
+def test_header_pass_fails_loudly_on_what_it_does_not_map_or_parse():
+    """_lib.signatures is a parser for this header, not for C: a parameter or return type outside the fixed mapping and any text the
+    prototype expression does not consume raise, naming the offender -- a new entry point cannot be bound unchecked."""
+    ok = '#ifdef __cplusplus\nextern "C" {\n#endif\n/* c */ typedef struct cg_s { int a; } cg_s;\nint cg_f(const cg_s* s, long n);\n}\n'
+    assert _lib.signatures(ok) == {'cg_f': (ctypes.c_int, (ctypes.c_void_p, ctypes.c_long))}
+    with pytest.raises(_lib.CatgraspAmdError, match=r"'cg_s s' of cg_f"):
+        _lib.signatures(ok.replace('const cg_s* s', 'cg_s s'))                 # struct by value
+    with pytest.raises(_lib.CatgraspAmdError, match=r'return value of cg_f.*short'):
+        _lib.signatures(ok.replace('int cg_f', 'short cg_f'))
+    with pytest.raises(_lib.CatgraspAmdError, match=r'cg_f'):
+        _lib.signatures(ok.replace('long n', 'int n[3]'))                      # array parameter
+    with pytest.raises(_lib.CatgraspAmdError, match=r'cannot parse.*other_entry'):
+        _lib.signatures(ok.replace('}\n', 'int other_entry(int a);\n}\n'))    # not a cg_ prototype: unparsed remainder
+    with pytest.raises(_lib.CatgraspAmdError, match=r'cannot parse.*cg_cb'):
+        _lib.signatures(ok.replace('}\n', 'int cg_g(int (*cg_cb)(int));\n}\n'))  # function pointer
+
+
 def test_argument_errors_are_reported_not_crashed():
     """Argument validation happens before any device work, so it can be exercised without a GPU."""
     lib = _lib.lib()
