@@ -7,6 +7,8 @@ Call graph per PointNetCls.forward (pointnet2.py:289-299), B samples of N points
           3x cg_gemm_bias_act             STNkd fc1,fc2,fc3 + I64              (B,4096)
   pass C  cg_pointmlp_max(mid 2, t3,t64)  enc.conv1, .T64, conv2, conv3, max   (B,1024)
           3x cg_gemm_bias_act             fc1,fc2,fc3                          (B,n_out)
+The sequence is written once (encoder_forward) for every arithmetic mode; what a mode changes about a launch -- kernel, weight
+images, tile geometry, range status -- is decided in _point_pass for the fused passes and in _dense for the GEMMs.
 """
 import os
 import threading
@@ -161,83 +163,53 @@ def _identity_t64(B, device):
     return torch.eye(64, dtype=torch.float32, device=device).reshape(1, 4096).repeat(B, 1).contiguous()
 
 
+def _point_pass(W, x, w1, tag, relu3, status, mid=None, **kw):
+    """One fused per-point pass (first layer `w1`, the 64 -> 128 -> 1024 layers of `tag`, optionally the 64 -> 64 layer `mid` in
+    between, max over the points) on the kernel of the active arithmetic -- the ONE place that turns the mode into weight images,
+    kernel, tile geometry and range-status forwarding.  'f32': the packed f32 images on 64-point tiles.  Split modes: 256-point
+    tiles and the bf16 ('.s') images, or -- under the half-based modes, when EVERY image of the pass fits the half pieces
+    (folding.put_half) -- the IEEE-half ('.h') ones, which report range excursions in `status`; under 'f16fp8x2' the 128 -> 1024
+    layer of such a pass takes its e4m3 ('.q') image."""
+    B, N, _ = x.shape
+    mode = current_precision()
+    names = [tag + '.w2', tag + '.w3'] + ([mid] if mid else [])
+    if mode == 'f32':
+        sfx = q = ''
+        kw.update(nsplit=_nsplit(B, N))
+    else:
+        half = mode in HALF_MODES and all(W.half_ok.get(n + '.h', False) for n in names)
+        sfx = '.h' if half else '.s'
+        q = '.q' if half and mode == 'f16fp8x2' else sfx
+        kw.update(nsplit=_nsplit(B, N, TILE_POINTS), tile_points=TILE_POINTS, split={'.s': 'bf16', '.h': 'f16', '.q': 'f16fp8'}[q],
+                  status=status if half else None)
+    if mid:
+        kw.update(wm=W[mid + sfx], bm=W[mid[:-3] + '.bm'])
+    return ops.pointmlp_max(x, W[w1 + '.w1'], W[w1 + '.b1'], W[tag + '.w2' + sfx], W[tag + '.b2'], W[tag + '.w3' + q], W[tag + '.b3'], relu3, **kw)
+
+
+def _tnet_tail(W, tag, g, k, status):
+    """The FC tail of an STN3d (k = 3) / STNkd (k = 64) on the pooled feature g (B,1024) -> (B,k*k) transform + I_k."""
+    h = _dense(W, tag + '.fc1', g, 512, W[tag + '.fc1b'], relu=True, status=status)
+    h = _dense(W, tag + '.fc2', h, 256, W[tag + '.fc2b'], relu=True, status=status)
+    return _dense(W, tag + '.fc3', h, k * k, W[tag + '.fc3b'], eye_k=k, status=status)
+
+
 def encoder_forward(W, x, want_pointfeat=False, status=None):
     """x:(B,N,6) cuda f32 -> global feature (B,1024), trans (B,9), trans_feat TRANSPOSED (B,4096) [, pointfeat].
     For an encoder without a feature transform (W.has_fstn False) trans_feat is None and pass B is skipped."""
-    if current_precision() != 'f32':
-        return _encoder_forward_split(W, x, want_pointfeat, status)
-    B, N, _ = x.shape
-    ns = _nsplit(B, N)
-    g = ops.pointmlp_max(x, W['stn.w1'], W['stn.b1'], W['stn.w2'], W['stn.b2'], W['stn.w3'], W['stn.b3'], True,
-                         nsplit=ns)
-    h = _dense(W, 'stn.fc1', g, 512, W['stn.fc1b'], relu=True)
-    h = _dense(W, 'stn.fc2', h, 256, W['stn.fc2b'], relu=True)
-    t3 = _dense(W, 'stn.fc3', h, 9, W['stn.fc3b'], eye_k=3)
-    if not getattr(W, 'has_fstn', True):
-        r = ops.pointmlp_max(x, W['enc.w1'], W['enc.b1'], W['enc.w2'], W['enc.b2'], W['enc.w3'], W['enc.b3'], False,
-                             t3=t3, mid_mode=2, t64=_identity_t64(B, x.device), nsplit=ns, pointfeat=want_pointfeat)
-        return (r[0], t3, None, r[1]) if want_pointfeat else (r, t3, None)
-    g = ops.pointmlp_max(x, W['enc.w1'], W['enc.b1'], W['fstn.w2'], W['fstn.b2'], W['fstn.w3'], W['fstn.b3'], True,
-                         t3=t3, mid_mode=1, wm=W['fstn.wm'], bm=W['fstn.bm'], nsplit=ns)
-    h = _dense(W, 'fstn.fc1', g, 512, W['fstn.fc1b'], relu=True)
-    h = _dense(W, 'fstn.fc2', h, 256, W['fstn.fc2b'], relu=True)
-    t64 = _dense(W, 'fstn.fc3', h, 4096, W['fstn.fc3b'], eye_k=64)
-    r = ops.pointmlp_max(x, W['enc.w1'], W['enc.b1'], W['enc.w2'], W['enc.b2'], W['enc.w3'], W['enc.b3'], False,
-                         t3=t3, mid_mode=2, t64=t64, nsplit=ns, pointfeat=want_pointfeat)
-    if want_pointfeat:
-        return r[0], t3, t64, r[1]
-    return r, t3, t64
-
-
-def _encoder_forward_split(W, x, want_pointfeat=False, status=None):
-    """encoder_forward with the split-precision per-point MLP kernels ('f16x3' or 'bf16x3').  Under 'f16x3' a pass whose
-    pre-split weight images do not fit the half pieces (folding.put_half: non-finite in half, or all below 2^-6) runs with
-    the bf16 images instead."""
-    B, N, _ = x.shape
-    ns = _nsplit(B, N, TILE_POINTS)
-
-    def point_pass(w1, tag, relu3, mid=None, **kw):
-        names = [tag + '.w2', tag + '.w3'] + ([mid] if mid else [])
-        half = current_precision() in HALF_MODES and all(W.half_ok.get(n + '.h', False) for n in names)
-        sfx = '.h' if half else '.s'
-        mx = half and current_precision() == 'f16fp8x2'
-        extra = dict(wm=W[mid + sfx], bm=W[mid[:-3] + '.bm']) if mid else {}
-        return ops.pointmlp_max(x, W[w1 + '.w1'], W[w1 + '.b1'], W[tag + '.w2' + sfx], W[tag + '.b2'], W[tag + '.w3' + ('.q' if mx else sfx)], W[tag + '.b3'],
-                                relu3, nsplit=ns, split=('f16fp8' if mx else 'f16') if half else 'bf16', tile_points=TILE_POINTS,
-                                status=status if half else None, **extra, **kw)
-
-    g = point_pass('stn', 'stn', True)
-    h = _dense(W, 'stn.fc1', g, 512, W['stn.fc1b'], relu=True, status=status)
-    h = _dense(W, 'stn.fc2', h, 256, W['stn.fc2b'], relu=True, status=status)
-    t3 = _dense(W, 'stn.fc3', h, 9, W['stn.fc3b'], eye_k=3)
-    if not getattr(W, 'has_fstn', True):
-        r = point_pass('enc', 'enc', False, t3=t3, mid_mode=2, t64=_identity_t64(B, x.device), pointfeat=want_pointfeat)
-        return (r[0], t3, None, r[1]) if want_pointfeat else (r, t3, None)
-    g = point_pass('enc', 'fstn', True, mid='fstn.wm', t3=t3, mid_mode=1)
-    h = _dense(W, 'fstn.fc1', g, 512, W['fstn.fc1b'], relu=True, status=status)
-    h = _dense(W, 'fstn.fc2', h, 256, W['fstn.fc2b'], relu=True, status=status)
-    t64 = _dense(W, 'fstn.fc3', h, 4096, W['fstn.fc3b'], eye_k=64, status=status)
-    r = point_pass('enc', 'enc', False, t3=t3, mid_mode=2, t64=t64, pointfeat=want_pointfeat)
-    if want_pointfeat:
-        return r[0], t3, t64, r[1]
-    return r, t3, t64
+    t3 = stn3d_forward(W, x, status)
+    t64 = None
+    if getattr(W, 'has_fstn', True):
+        g = _point_pass(W, x, 'enc', 'fstn', True, status, mid='fstn.wm', t3=t3, mid_mode=1)
+        t64 = _tnet_tail(W, 'fstn', g, 64, status)
+    r = _point_pass(W, x, 'enc', 'enc', False, status, t3=t3, mid_mode=2, t64=t64 if t64 is not None else _identity_t64(x.shape[0], x.device),
+                    pointfeat=want_pointfeat)
+    return (r[0], t3, t64, r[1]) if want_pointfeat else (r, t3, t64)
 
 
 def stn3d_forward(W, x, status=None):
-    """A standalone STN3d (pointnet2.py:170-185).  x:(B,N,6) -> (B,9) row-major 3x3."""
-    B, N, _ = x.shape
-    if current_precision() == 'f32':
-        g = ops.pointmlp_max(x, W['stn.w1'], W['stn.b1'], W['stn.w2'], W['stn.b2'], W['stn.w3'], W['stn.b3'], True, nsplit=_nsplit(B, N))
-    else:
-        half = current_precision() in HALF_MODES and all(W.half_ok.get(n + '.h', False) for n in ('stn.w2', 'stn.w3'))
-        sfx = '.h' if half else '.s'
-        mx = half and current_precision() == 'f16fp8x2'
-        g = ops.pointmlp_max(x, W['stn.w1'], W['stn.b1'], W['stn.w2' + sfx], W['stn.b2'], W['stn.w3' + ('.q' if mx else sfx)], W['stn.b3'], True,
-                             nsplit=_nsplit(B, N, TILE_POINTS), split=('f16fp8' if mx else 'f16') if half else 'bf16', tile_points=TILE_POINTS,
-                             status=status if half else None)
-    h = _dense(W, 'stn.fc1', g, 512, W['stn.fc1b'], relu=True, status=status)
-    h = _dense(W, 'stn.fc2', h, 256, W['stn.fc2b'], relu=True, status=status)
-    return _dense(W, 'stn.fc3', h, 9, W['stn.fc3b'], eye_k=3)
+    """A standalone STN3d (pointnet2.py:170-185), and pass A of the encoder.  x:(B,N,6) -> (B,9) row-major 3x3."""
+    return _tnet_tail(W, 'stn', _point_pass(W, x, 'stn', 'stn', True, status), 3, status)
 
 
 def stnkd_forward(W, x):
@@ -333,7 +305,7 @@ def cls_forward(W, x, status=None):
     g, t3, t64 = encoder_forward(W, x, status=status)
     h = _dense(W, 'head.fc1', g, 512, W['head.fc1b'], relu=True, status=status)
     h = _dense(W, 'head.fc2', h, 256, W['head.fc2b'], relu=True, status=status)
-    logits = _dense(W, 'head.fc3', h, W.n_out, W['head.fc3b'])
+    logits = _dense(W, 'head.fc3', h, W.n_out, W['head.fc3b'], status=status)
     return logits, t64.view(B, 64, 64).transpose(1, 2)      # the FC kernel emits the transform transposed
 
 

@@ -160,7 +160,7 @@ class DeviceWeights:
         """IEEE-half split image of a folded weight matrix + the pre-screen of its range: the image is used by the f16x3
         kernels only if every weight is finite in half (|w| < 65504 after BN folding -- a blown-up BN scale can exceed it) and
         the matrix is not uniformly tiny (max |w| >= 2^-6: below that the lo pieces sit in the half subnormals).  Layers that
-        fail the screen run with bf16 pieces / exact f32 instead (engine._dense, engine._encoder_forward_split)."""
+        fail the screen run with bf16 pieces / exact f32 instead (engine._dense, engine._point_pass)."""
         w = np.asarray(w, dtype=np.float32)
         if not np.isfinite(w).all():
             raise ValueError(f'non-finite folded weights in layer {name[:-2]} (checkpoint or BatchNorm statistics are corrupt)')

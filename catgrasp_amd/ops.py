@@ -14,45 +14,35 @@ from ._lib import _p, _stream, check, f32c, i32c, require_cuda
 KERNEL_TIMER = None
 
 
+# split -> (C symbol, takes tile_points, takes status) of the fused per-point pass
+_POINTMLP_KERNELS = {False: ('cg_pointmlp_max', False, False), 'bf16': ('cg_pointmlp_max_bf16x3', True, False),
+                     'f16': ('cg_pointmlp_max_f16x3', True, True), 'f16fp8': ('cg_pointmlp_max_f16fp8x2', True, True)}
+
+
 def pointmlp_max(x, w1, b1, w2p, b2, w3p, b3, relu3, t3=None, mid_mode=0, wm=None, bm=None, t64=None,
                  nsplit=1, pointfeat=False, split=False, tile_points=256, status=None):
     """x:(B,N,6) -> (B,1024) [, pointfeat (B,N,64)].  See cg_pointmlp_max / cg_pointmlp_max_bf16x3 in
     include/catgrasp_amd.h.  split='f16' / 'bf16': w2p/w3p/wm are the split images of that element type (folding.pack_b_split);
-    split='f16fp8': as 'f16' except that w3p is the f16fp8x2 image of the 128 -> 1024 layer (folding.pack_b_f16fp8x2)."""
+    split='f16fp8': as 'f16' except that w3p is the f16fp8x2 image of the 128 -> 1024 layer (folding.pack_b_f16fp8x2).
+    status (half-based kernels only): caller-owned device int that collects the half range bits (None: not tracked)."""
     require_cuda(x)
     f32c(x)
     B, N, D = x.shape
     assert D == 6
     out = torch.empty((B, 1024), dtype=torch.float32, device=x.device)
     pf = torch.empty((B, N, 64), dtype=torch.float32, device=x.device) if pointfeat else None
-    if split:
-        timer = KERNEL_TIMER if (KERNEL_TIMER is not None and KERNEL_TIMER['mid_mode'] == mid_mode) else None
-        if timer is not None:
-            ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        args = (_p(x), B, N, _p(t3), _p(w1), _p(b1), mid_mode, _p(wm), _p(bm),
-                _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), int(relu3), nsplit, tile_points, _p(out), _p(pf))
-        if split == 'f16':      # status: caller-owned device int that collects the half range bits (None: not tracked)
-            st = L.lib().cg_pointmlp_max_f16x3(*args, _p(status), _stream())
-        elif split == 'f16fp8':
-            st = L.lib().cg_pointmlp_max_f16fp8x2(*args, _p(status), _stream())
-        else:
-            st = L.lib().cg_pointmlp_max_bf16x3(*args, _stream())
-        if timer is not None:
-            ev1.record()
-            timer['events'].append((ev0, ev1, (B, N)))
-        check(st, {'f16': 'cg_pointmlp_max_f16x3', 'f16fp8': 'cg_pointmlp_max_f16fp8x2'}.get(split, 'cg_pointmlp_max_bf16x3'))
-        return (out, pf) if pointfeat else out
+    name, has_tile, has_status = _POINTMLP_KERNELS[split or False]
+    args = (_p(x), B, N, _p(t3), _p(w1), _p(b1), mid_mode, _p(wm), _p(bm), _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), int(relu3), nsplit,
+            *((tile_points,) if has_tile else ()), _p(out), _p(pf), *((_p(status),) if has_status else ()), _stream())
     timer = KERNEL_TIMER if (KERNEL_TIMER is not None and KERNEL_TIMER['mid_mode'] == mid_mode) else None
     if timer is not None:
         ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-    st = L.lib().cg_pointmlp_max(_p(x), B, N, _p(t3), _p(w1), _p(b1), mid_mode, _p(wm), _p(bm), _p(t64), _p(w2p), _p(b2), _p(w3p), _p(b3), int(relu3),
-                                 nsplit, _p(out), _p(pf), _stream())
+    st = getattr(L.lib(), name)(*args)
     if timer is not None:
         ev1.record()
         timer['events'].append((ev0, ev1, (B, N)))
-    check(st, 'cg_pointmlp_max')
+    check(st, name)
     return (out, pf) if pointfeat else out
 
 

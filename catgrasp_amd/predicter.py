@@ -109,6 +109,16 @@ def _device(device):
     return torch.device('cuda', torch.cuda.current_device())
 
 
+def _chunk_bounds(G, chunk, ramp=()):
+    """[(s, e), ...] covering range(G) in order: one chunk per size of `ramp` (each capped at `chunk`), then full chunks."""
+    sizes = [min(chunk, r) for r in ramp]
+    bounds, s = [], 0
+    while s < G:
+        e = min(G, s + (sizes.pop(0) if sizes else chunk))
+        bounds.append((s, e)); s = e
+    return bounds
+
+
 class _TransformOnly:
     """Stand-in for the `.dataset` attribute of the reference predicters (predicter.py:60,127): keeps cfg /
     phase; the transform itself runs on the device inside predict*()."""
@@ -165,11 +175,7 @@ class GraspPredicter:
         logits = torch.empty((G, C), dtype=torch.float32, device=self.device)
         # chunk boundaries: uniform, or -- for an id source that is produced on the host while the device works (ids.ramp) -- a
         # short first chunk doubling up to the full size, so that the device starts after a fraction of the first draw
-        sizes = [min(self.chunk, r) for r in getattr(ids, 'ramp', ())]
-        bounds, s = [], 0
-        while s < G:
-            e = min(G, s + (sizes.pop(0) if sizes else self.chunk))
-            bounds.append((s, e)); s = e
+        bounds = _chunk_bounds(G, self.chunk, getattr(ids, 'ramp', ()))
         if hasattr(ids, 'plan'):
             ids.plan(bounds)
         starts = [b[0] for b in bounds]
@@ -260,11 +266,7 @@ class GraspPredicter:
         and the host stays AHEAD during the ramp: the exact-f32 network takes ~12 us per candidate, the replay of numpy's stream ~6 us,
         so a doubling ramp is a dead heat (chunk k+1 is drawn in exactly the time chunk k is scored) and any slower host core stalls
         the device at every step of it; 1.5x leaves 25 % slack."""
-        sizes = [min(self.chunk, r) for r in (1024, 1536, 2304, 3456, 5184, 7776, 11664)]
-        bounds, s = [], 0
-        while s < G:
-            e = min(G, s + (sizes.pop(0) if sizes else self.chunk))
-            bounds.append((s, e)); s = e
+        bounds = _chunk_bounds(G, self.chunk, (1024, 1536, 2304, 3456, 5184, 7776, 11664))
         if hasattr(id_source, 'plan'):
             id_source.plan(bounds)
         return bounds
