@@ -231,10 +231,11 @@ class PointNetSeg(_HipCached):
         return self.conv4(h).permute(0, 2, 1), trans_feat
 
 
-def _sa_layers_from_state(sd, prefix, n):
+def _sa_layers_from_state(sd, prefix, n, conv='convs', bn='bns'):
+    """The n [conv, bn] layers `{prefix}{conv}.{i}` / `{prefix}{bn}.{i}` of a state dict, as SetAbstractionWeights takes them."""
     g = lambda k: sd[k].detach().cpu().double().numpy()
-    return [(g(f'{prefix}convs.{i}.weight'), g(f'{prefix}convs.{i}.bias'),
-             tuple(g(f'{prefix}bns.{i}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var'))) for i in range(n)]
+    return [(g(f'{prefix}{conv}.{i}.weight'), g(f'{prefix}{conv}.{i}.bias'),
+             tuple(g(f'{prefix}{bn}.{i}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var'))) for i in range(n)]
 
 
 def _mlp_torch(h, convs, bns):
@@ -243,7 +244,56 @@ def _mlp_torch(h, convs, bns):
     return h
 
 
-class PointNetSetAbstraction(nn.Module):
+class _SetAbstractionLevel(nn.Module):
+    """The one body of a SAMPLING set-abstraction level, single- or multi-scale: ONE farthest-point sample of `npoint` points, then per scale
+    query_ball_point -> group -> shared MLP -> max over the neighbours, the scales' outputs side by side along the channels.  A subclass
+    says what its scales are: _scales() -> [(radius, nsample, convs, bns)], _scale_weights(device) -> [SetAbstractionWeights], and
+    _INDEX_ERROR, the name its index errors are reported under.  (The group-all level is PointNetSetAbstraction's own branch.)"""
+
+    def forward(self, xyz, points, start=None):
+        if _use_hip(self, xyz):
+            return self._hip_forward(xyz, points, start)
+        return self._torch_forward(xyz, points, start)
+
+    def _hip_forward(self, xyz, points, start=None, new_xyz=None, rows=None, err=None):
+        """Every scale's fused kernel writes its channel slice of the output directly (strided store); nothing is concatenated.
+        The arguments past `start` are PointNet2Encoder's:
+        new_xyz: the level's sampled points when the stack has already run its farthest-point sampling (on a side stream).
+        rows: a (B, S, roundup8(C + 3)) buffer to produce the output in -- features in [..., :C] (the returned new_points is that view), the
+        level's new_xyz ++ zeros behind them, written by the last scale's kernel: the input rows of a following group-all level.
+        err: a pre-zeroed (1,) int32 device flag shared by the levels of a stack (one read-back for the stack instead of one per level)."""
+        Ws = self._scale_weights(xyz.device)
+        C = sum(W.cout[-1] for W in Ws)
+        if new_xyz is None:
+            _, new_xyz = farthest_point_sample(xyz, self.npoint, start, return_xyz=True)      # = index_points(xyz, fps_idx), same launch
+        buf = rows if rows is not None else torch.empty((xyz.shape[0], self.npoint, C), dtype=torch.float32, device=xyz.device)
+        flag = torch.zeros((1,), dtype=torch.int32, device=xyz.device) if err is None else err
+        c0 = 0
+        for i, (W, (radius, K, _, _)) in enumerate(zip(Ws, self._scales())):
+            idx = query_ball_point(radius, K, xyz, new_xyz)
+            last = rows is not None and i == len(Ws) - 1
+            _prim.group_mlp_max(xyz, points, new_xyz, idx, W, check_indices=False, channels_last=True, out=buf[:, :, c0:c0 + W.cout[-1]],
+                                append_xyz=buf.shape[-1] - C if last else 0, err=flag)
+            c0 += W.cout[-1]
+        if err is None:
+            _prim._raise_if(flag, f'{self._INDEX_ERROR} (a query ball was empty or an index is out of range)')
+        return new_xyz, buf[:, :, :C]
+
+    def _torch_forward(self, xyz, points, start):
+        """Indices from the HIP kernels (or torch ops on a CPU tensor); the gathers are differentiable torch indexing."""
+        fps_idx = farthest_point_sample(xyz, self.npoint, start) if xyz.is_cuda else _torch_fps(xyz, self.npoint, start)
+        new_xyz = _torch_index(xyz, fps_idx)
+        outs = []
+        for radius, K, convs, bns in self._scales():
+            idx = query_ball_point(radius, K, xyz, new_xyz) if xyz.is_cuda else _torch_ball(radius, K, xyz, new_xyz)
+            grouped = _torch_index(xyz, idx) - new_xyz.unsqueeze(2)
+            if points is not None:
+                grouped = torch.cat([grouped, _torch_index(points, idx)], dim=-1)
+            outs.append(torch.max(_mlp_torch(grouped.permute(0, 3, 2, 1), convs, bns), 2)[0])      # (B, 3+D, K, S) -> (B, C, K, S) -> (B, C, S)
+        return new_xyz, torch.cat(outs, dim=1).permute(0, 2, 1)
+
+
+class PointNetSetAbstraction(_SetAbstractionLevel):
     """The set-abstraction layer the reference's primitives were written for (pointnet2.py:14-149 define sample_and_group and
     friends, but the reference never assembles them into a layer -- SURVEY.md §0 F1; BASELINE.json's north_star names it):
         new_xyz, new_points = sample_and_group(npoint, radius, nsample, xyz, points)      [group_all: sample_and_group_all(xyz, points)]
@@ -252,6 +302,8 @@ class PointNetSetAbstraction(nn.Module):
     Eval-mode inference on a HIP tensor: FPS + ball query + ONE fused group->MLP->max kernel (primitives.group_mlp_max: the
     register-resident kernel for a first layer, the LDS-tile kernel for 3 + D > 16 inputs or wider layers), the grouped tensor never
     exists; group_all: primitives.group_all_mlp_max.  Training / grad-enabled calls use the torch ops on the grouped tensor."""
+
+    _INDEX_ERROR = 'group_mlp_max'
 
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all=False):
         super().__init__()
@@ -268,55 +320,37 @@ class PointNetSetAbstraction(nn.Module):
         return _cached_weights(self, device, lambda sd, dev: _prim.SetAbstractionWeights(_sa_layers_from_state(sd, 'mlp_', n), self.in_channel,
                                                                                           dev, kind=kind))
 
-    def forward(self, xyz, points, start=None, _err=None, _rows=None, _new_xyz=None, _validated=False):
-        """_new_xyz (stack-internal): the level's sampled points when the stack has already run its farthest-point sampling (on a side stream).
-        _err: a pre-zeroed (1,) int32 device flag shared by the levels of a stack (one read-back for the stack instead of one per layer).
-        _rows (stack-internal): for a sampling level, a (B, S, roundup8(C + 3)) buffer to produce the output in -- features in
-        [..., :C] (the returned new_points is that view), the level's new_xyz ++ zeros behind them, i.e. the input rows of a following
-        group-all level; for the group-all level, that buffer.
-        _validated (stack-internal): the stack has checked its input for NaN / Inf once (no further host synchronisation per level)."""
-        if _use_hip(self, xyz, _validated):
-            W = self._weights(xyz.device)
-            if self.group_all:
-                B = xyz.shape[0]
-                rows = None if _rows is None else _rows.view(-1, _rows.shape[-1])
-                return (torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device),
-                        _prim.group_all_mlp_max(xyz, points, W, rows=rows).view(B, 1, -1))
-            new_xyz = _new_xyz
-            if new_xyz is None:
-                _, new_xyz = farthest_point_sample(xyz, self.npoint, start, return_xyz=True)      # = index_points(xyz, fps_idx), same launch
-            idx = query_ball_point(self.radius, self.nsample, xyz, new_xyz)
-            kw = {}
-            if _rows is not None:
-                C = W.cout[-1]
-                kw = {'out': _rows[:, :, :C]}
-                if W.kind == 'tile':
-                    kw['append_xyz'] = _rows.shape[-1] - C
-                else:                      # a first-layer shape feeding a group-all level directly: the three columns by a copy
-                    _rows[:, :, C:C + 3] = new_xyz; _rows[:, :, C + 3:] = 0
-            if _err is not None:
-                return new_xyz, _prim.group_mlp_max(xyz, points, new_xyz, idx, W, check_indices=False, channels_last=True, err=_err, **kw)[0]
-            return new_xyz, _prim.group_mlp_max(xyz, points, new_xyz, idx, W, channels_last=True, **kw)
-        if self.group_all:
-            new_xyz, new_points = sample_and_group_all(xyz, points)
-        else:       # indices from the HIP kernels (or torch ops on a CPU tensor); the gathers are differentiable torch indexing
-            fps_idx = farthest_point_sample(xyz, self.npoint, start) if xyz.is_cuda else _torch_fps(xyz, self.npoint, start)
-            new_xyz = _torch_index(xyz, fps_idx)
-            idx = query_ball_point(self.radius, self.nsample, xyz, new_xyz) if xyz.is_cuda else _torch_ball(self.radius, self.nsample, xyz, new_xyz)
-            new_points = _torch_index(xyz, idx) - new_xyz.unsqueeze(2)
-            if points is not None:
-                new_points = torch.cat([new_points, _torch_index(points, idx)], dim=-1)
-        h = _mlp_torch(new_points.permute(0, 3, 2, 1), self.mlp_convs, self.mlp_bns)          # (B, 3+D, K, S) -> (B, C, K, S)
+    def _scales(self):
+        return [(self.radius, self.nsample, self.mlp_convs, self.mlp_bns)]
+
+    def _scale_weights(self, device):
+        return [self._weights(device)]
+
+    def _hip_forward(self, xyz, points, start=None, new_xyz=None, rows=None, err=None):
+        """group_all: `rows` is the (B, N, cin) [features | xyz | pad] buffer the level before has written (_SetAbstractionLevel._hip_forward)."""
+        if not self.group_all:
+            return super()._hip_forward(xyz, points, start, new_xyz, rows, err)
+        B = xyz.shape[0]
+        rows = None if rows is None else rows.view(-1, rows.shape[-1])
+        return (torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device),
+                _prim.group_all_mlp_max(xyz, points, self._weights(xyz.device), rows=rows).view(B, 1, -1))
+
+    def _torch_forward(self, xyz, points, start):
+        if not self.group_all:
+            return super()._torch_forward(xyz, points, start)
+        new_xyz, new_points = sample_and_group_all(xyz, points)
+        h = _mlp_torch(new_points.permute(0, 3, 2, 1), self.mlp_convs, self.mlp_bns)          # (B, 3+D, N, 1) -> (B, C, N, 1)
         return new_xyz, torch.max(h, 2)[0].permute(0, 2, 1)
 
 
-class PointNetSetAbstractionMsg(nn.Module):
+class PointNetSetAbstractionMsg(_SetAbstractionLevel):
     """Multi-scale grouping: ONE farthest-point sample, then per scale i  query_ball_point(radius_list[i], nsample_list[i]) -> group ->
     shared MLP mlp_list[i] -> max, the scales' outputs concatenated along the channels (the multi-scale layer the primitives of
     pointnet2.py:54-129 build; north_star: "set-abstraction encoder").  in_channel = D, the feature channels WITHOUT the 3 coordinates
     (the convention of the usual PointNet++ code for this layer).  forward(xyz (B,N,3), points (B,N,D) | None) ->
-    (new_xyz (B,S,3), new_points (B,S,sum_i mlp_list[i][-1])).  HIP path: every scale's fused kernel writes its channel slice of the
-    output directly (strided store); nothing is concatenated."""
+    (new_xyz (B,S,3), new_points (B,S,sum_i mlp_list[i][-1]))."""
+
+    _INDEX_ERROR = 'PointNetSetAbstractionMsg'
 
     def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
         super().__init__()
@@ -332,46 +366,14 @@ class PointNetSetAbstractionMsg(nn.Module):
             self.conv_blocks.append(convs); self.bn_blocks.append(bns)
         self.out_channel = sum(m[-1] for m in mlp_list)
 
-    def forward(self, xyz, points, start=None, _err=None, _rows=None, _new_xyz=None, _validated=False):
-        if _use_hip(self, xyz, _validated):
-            def prep(sd, dev):
-                out = []
-                for i, convs in enumerate(self.conv_blocks):
-                    g = lambda k: sd[k].detach().cpu().double().numpy()
-                    layers = [(g(f'conv_blocks.{i}.{j}.weight'), g(f'conv_blocks.{i}.{j}.bias'),
-                               tuple(g(f'bn_blocks.{i}.{j}.{k}') for k in ('weight', 'bias', 'running_mean', 'running_var'))) for j in range(len(convs))]
-                    out.append(_prim.SetAbstractionWeights(layers, self.in_channel + 3, dev))
-                return out
-            Ws = _cached_weights(self, xyz.device, prep)
-            B = xyz.shape[0]
-            new_xyz = _new_xyz
-            if new_xyz is None:
-                _, new_xyz = farthest_point_sample(xyz, self.npoint, start, return_xyz=True)
-            buf = _rows if _rows is not None else torch.empty((B, self.npoint, self.out_channel), dtype=torch.float32, device=xyz.device)
-            out = buf[:, :, :self.out_channel]
-            err = torch.zeros((1,), dtype=torch.int32, device=xyz.device) if _err is None else _err
-            c0 = 0
-            for i, (W, radius, K) in enumerate(zip(Ws, self.radius_list, self.nsample_list)):
-                idx = query_ball_point(radius, K, xyz, new_xyz)
-                last = i == len(Ws) - 1 and _rows is not None and W.kind == 'tile'      # the last scale's kernel also writes xyz ++ pad
-                _prim.group_mlp_max(xyz, points, new_xyz, idx, W, check_indices=False, channels_last=True, out=out[:, :, c0:c0 + W.cout[-1]],
-                                    append_xyz=buf.shape[-1] - self.out_channel if last else 0, err=err)
-                c0 += W.cout[-1]
-            if _rows is not None and Ws[-1].kind != 'tile':
-                buf[:, :, self.out_channel:self.out_channel + 3] = new_xyz; buf[:, :, self.out_channel + 3:] = 0
-            if _err is None:
-                _prim._raise_if(err, 'PointNetSetAbstractionMsg (a query ball was empty or an index is out of range)')
-            return new_xyz, out
-        fps_idx = farthest_point_sample(xyz, self.npoint, start) if xyz.is_cuda else _torch_fps(xyz, self.npoint, start)
-        new_xyz = _torch_index(xyz, fps_idx)
-        outs = []
-        for convs, bns, radius, K in zip(self.conv_blocks, self.bn_blocks, self.radius_list, self.nsample_list):
-            idx = query_ball_point(radius, K, xyz, new_xyz) if xyz.is_cuda else _torch_ball(radius, K, xyz, new_xyz)
-            grouped = _torch_index(xyz, idx) - new_xyz.unsqueeze(2)
-            if points is not None:
-                grouped = torch.cat([grouped, _torch_index(points, idx)], dim=-1)
-            outs.append(torch.max(_mlp_torch(grouped.permute(0, 3, 2, 1), convs, bns), 2)[0])
-        return new_xyz, torch.cat(outs, dim=1).permute(0, 2, 1)
+    def _scales(self):
+        return list(zip(self.radius_list, self.nsample_list, self.conv_blocks, self.bn_blocks))
+
+    def _scale_weights(self, device):
+        def prep(sd, dev):
+            return [_prim.SetAbstractionWeights(_sa_layers_from_state(sd, '', len(convs), conv=f'conv_blocks.{i}', bn=f'bn_blocks.{i}'),
+                                                self.in_channel + 3, dev) for i, convs in enumerate(self.conv_blocks)]
+        return _cached_weights(self, device, prep)
 
 
 def _torch_index(points, idx):
@@ -460,13 +462,12 @@ class PointNet2Encoder(nn.Module):
         xyz = x[:, :, :3].contiguous()
         feats = x[:, :, 3:].contiguous() if C > 3 else None
         s1, s2 = (None, None) if start is None else start
-        # the fused stack needs EVERY level in eval mode: a level left in train mode (partial fine-tuning) takes its torch branch, which
-        # ignores the stack-internal arguments -- then each level decides for itself below
+        # the fused stack needs EVERY level in eval mode: with a level left in train mode (partial fine-tuning) each level decides for itself,
+        # through its public forward
         hip = not any(m.training for m in (self.sa1, self.sa2, self.sa3)) and _use_hip(self, x)
-        err = torch.zeros((1,), dtype=torch.int32, device=x.device) if hip else None
-        kw = {'_err': err, '_validated': True} if hip else {}       # x was checked once, above: no stream drain between the levels
-        rows = None
         if hip:
+            # x was checked once, above, and the levels' _hip_forward checks nothing: no stream drain between the levels
+            err = torch.zeros((1,), dtype=torch.int32, device=x.device)
             # Level 2's sampling chain needs level 1's sampled POINTS only, not its features: from SIDE_STREAM_MIN_CLOUDS clouds on it runs on
             # a side stream while level 1's ball query and fused kernel use the rest of the chip (a sampling chain occupies one CU per
             # cloud).  Measured (profiles/r5_pp_encoder_side_stream.json): 16 clouds 0.973 -> 0.948 ms, 8 clouds unchanged, ONE cloud
@@ -482,20 +483,20 @@ class PointNet2Encoder(nn.Module):
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
                     _, l2_xyz = fps(l1_xyz, self.sa2.npoint, s2)
-                _, l1_points = self.sa1(xyz, feats, _new_xyz=l1_xyz, **kw)
+                _, l1_points = self.sa1._hip_forward(xyz, feats, new_xyz=l1_xyz, err=err)
                 cur.wait_stream(side)
                 l2_xyz.record_stream(cur)
             else:
-                _, l1_points = self.sa1(xyz, feats, _new_xyz=l1_xyz, **kw)
+                _, l1_points = self.sa1._hip_forward(xyz, feats, new_xyz=l1_xyz, err=err)
                 _, l2_xyz = fps(l1_xyz, self.sa2.npoint, s2)
             # level 2 writes [features | xyz | pad] rows: what the group-all level's first GEMM reads (no concatenation pass)
             c2 = self.sa3.in_channel - 3
             rows = torch.empty((B, self.sa2.npoint, (c2 + 3 + 7) & ~7), dtype=torch.float32, device=x.device)
-            _, l2_points = self.sa2(l1_xyz, l1_points, _new_xyz=l2_xyz, _rows=rows, **kw)
+            _, l2_points = self.sa2._hip_forward(l1_xyz, l1_points, new_xyz=l2_xyz, rows=rows, err=err)
+            _, l3_points = self.sa3._hip_forward(l2_xyz, l2_points, rows=rows)
+            _prim._raise_if(err, 'PointNet2Encoder (a query ball was empty or an index is out of range)')
         else:
             l1_xyz, l1_points = self.sa1(xyz, feats, start=s1)
             l2_xyz, l2_points = self.sa2(l1_xyz, l1_points, start=s2)
-        _, l3_points = self.sa3(l2_xyz, l2_points, **({'_rows': rows, '_validated': True} if rows is not None else {}))
-        if hip:
-            _prim._raise_if(err, 'PointNet2Encoder (a query ball was empty or an index is out of range)')
+            _, l3_points = self.sa3(l2_xyz, l2_points)
         return l3_points.reshape(B, -1), [(l1_xyz, l1_points), (l2_xyz, l2_points)]
