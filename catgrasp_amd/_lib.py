@@ -9,6 +9,9 @@ TypeError; a float for an integer, a list for a pointer or a ctypes scalar of an
 ctypes.ArgumentError; a count >= 2**31 for a `long` arrives intact.  Every pointer parameter is a c_void_p: it takes `_p(tensor)`,
 None, an address, `byref(struct)` and ctypes arrays.  Two things ctypes does NOT catch: extra trailing arguments are passed
 through, and a `str` is accepted for a pointer.
+
+The clustering entry points have a header of their own, include/catgrasp_amd_cluster.h (same library): `signatures()` and
+`declared_symbols()` describe the main header, `cluster_signatures()` the other, and `lib()` binds and requires both.
 """
 import ctypes
 import os
@@ -19,6 +22,7 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CATGRASP_AMD_LIB', os.path.join(_PKG, 'libcatgrasp_amd.so'))   # override: dev ablation builds only
 HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd.h')
+CLUSTER_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_cluster.h')   # the clustering entry points: their own header
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -64,6 +68,12 @@ def declared_symbols():
     return sorted(signatures())
 
 
+def cluster_signatures():
+    """signatures() of include/catgrasp_amd_cluster.h: same parser, same type mapping."""
+    with open(CLUSTER_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -72,7 +82,7 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -m catgrasp_amd.build` '
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
-        sigs = signatures()
+        sigs = {**signatures(), **cluster_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')

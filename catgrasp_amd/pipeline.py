@@ -364,3 +364,10 @@ def _evaluate_objects_overlapped(objects, scene_pts, K, gripper, grasp_predicter
     if timings is not None:
         timings.extend(tms)
     return results
+
+
+def objects_from_segmentation(cloud_xyz, cloud_normal, labels, order):
+    """The object list `evaluate_objects` consumes, from `segmentation.select_segments`' cleaned labels and pick order
+    (run_grasp_simulation.py:266-280: one object per surviving segment id, in that order)."""
+    xyz, nrm, labels = np.asarray(cloud_xyz), np.asarray(cloud_normal), np.asarray(labels)
+    return [{'ob_pts': xyz[labels == seg_id], 'ob_normals': nrm[labels == seg_id]} for seg_id in order]
