@@ -11,7 +11,8 @@ None, an address, `byref(struct)` and ctypes arrays.  Two things ctypes does NOT
 through, and a `str` is accepted for a pointer.
 
 The clustering entry points have a header of their own, include/catgrasp_amd_cluster.h (same library): `signatures()` and
-`declared_symbols()` describe the main header, `cluster_signatures()` the other, and `lib()` binds and requires both.
+`declared_symbols()` describe the main header, `cluster_signatures()` the other.  The sparse convolution layers have a third,
+include/catgrasp_amd_sparse.h, described by `sparse_signatures()`.  `lib()` binds and requires all three.
 """
 import ctypes
 import os
@@ -23,6 +24,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CATGRASP_AMD_LIB', os.path.join(_PKG, 'libcatgrasp_amd.so'))   # override: dev ablation builds only
 HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd.h')
 CLUSTER_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_cluster.h')   # the clustering entry points: their own header
+SPARSE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_sparse.h')     # the sparse convolution layers: likewise
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -74,6 +76,12 @@ def cluster_signatures():
         return signatures(f.read())
 
 
+def sparse_signatures():
+    """signatures() of include/catgrasp_amd_sparse.h: same parser, same type mapping."""
+    with open(SPARSE_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -82,7 +90,7 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -m catgrasp_amd.build` '
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
-        sigs = {**signatures(), **cluster_signatures()}
+        sigs = {**signatures(), **cluster_signatures(), **sparse_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')
