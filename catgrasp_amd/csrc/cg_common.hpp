@@ -51,3 +51,53 @@ static inline int cg_device_cu_count(int dev) {
   }
   return n_cu[dev];
 }
+
+// Allow `kernel` `bytes` of dynamic LDS on device `dev` (anything above the 64 KB default needs it).  The attribute is per device, so
+// it is set once per (kernel, device): done[CG_MAX_DEVICES] is the caller's flag row for that kernel.
+static inline int cg_allow_dynamic_lds(const void* kernel, int dev, size_t bytes, bool* done) {
+  if (dev < 0 || dev >= CG_MAX_DEVICES) return CG_ERR_UNSUPPORTED;
+  if (!done[dev]) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return (int)e;
+    done[dev] = true;
+  }
+  return CG_OK;
+}
+// the kernel known at compile time: its flag row lives here
+template <auto Kernel>
+int cg_allow_dynamic_lds(int dev, size_t bytes) {
+  static bool done[CG_MAX_DEVICES] = {};
+  return cg_allow_dynamic_lds((const void*)Kernel, dev, bytes, done);
+}
+
+// Launch plan of the fused per-point MLP + max-pool entry points (pointmlp.hip, which defines it, and pointmlp_split.hip), for B samples
+// of ntiles point tiles each and the caller's nsplit workgroups per sample:
+//  * nsplit is clamped to [1, ntiles];
+//  * tail balancing: with one workgroup per sample (nsplit == 1) and B >= the resident workgroups (slots_per_cu per CU), the B % slots
+//    samples of the last, partially filled scheduling round would occupy a few CUs for a whole sample's duration while the rest of the
+//    chip idles; from min_tiles tiles on they are split tail_split ways instead (n_main = the samples before them), so that round is short;
+//  * rows written by more than one workgroup (atomic max) are pre-filled with -inf: all of out (B, 1024) when nsplit > 1, the tail's rows
+//    otherwise.
+// status != CG_OK: nothing was launched.
+struct CgPointMlpPlan { int status, dev, nsplit, n_main, tail_split; };
+CgPointMlpPlan cg_pointmlp_plan(int B, int ntiles, int nsplit, int slots_per_cu, int min_tiles, int tail_split, float* out, hipStream_t s);
+
+// Head of the dense-layer kernels' epilogue (gemm.hip, gemm_split.hip; A = their argument struct): the column's bias incl. the flattened
+// identity (eye_k > 0: + I_k, col = i*k + i).  The rest of the epilogue -- per-group bias, ReLU, guarded store -- stays written out in
+// each kernel: moved into a function (by reference, by value, per tile or per element) it changed the register allocation of all four.
+template <typename A>
+__device__ __forceinline__ float cg_gemm_col_bias(const A& a, int col) {
+  float bias = a.bias ? a.bias[col] : 0.f;
+  if (a.eye_k > 0 && (col % (a.eye_k + 1)) == 0) bias += 1.f;
+  return bias;
+}
+
+// Argument check shared by the dense-layer entry points (K a multiple of k_mult: 8 for the f32 kernels' k-steps, 16 for the split ones')
+static inline int cg_gemm_check_args(const float* x, int M, int K, int ldx, const void* w, int N, const float* row_bias, int rows_per_group,
+                                     int ld_rb, const float* y, int ldy, int k_mult) {
+  if (!x || !w || !y) return CG_ERR_ARG;
+  if (M < 0 || N <= 0 || K <= 0 || (K % k_mult) != 0 || (ldx % 4) != 0 || ldx < K || ldy < N) return CG_ERR_ARG;
+  if (((uintptr_t)x & 15) != 0) return CG_ERR_ARG;
+  if (row_bias && (rows_per_group <= 0 || ld_rb < N)) return CG_ERR_ARG;
+  return CG_OK;
+}

@@ -698,7 +698,7 @@ inline Mesh make_mesh(const float* V, const int* F, int nf, const cg_mesh_grid* 
   return m;
 }
 
-// Workgroups the collision kernels are launched with at most (grid-stride beyond): 16 per CU.  CATGRASP_AMD_FILTER_BLOCKS_PER_CU (dev
+// Workgroups the collision kernels are launched with at most (grid-stride beyond): 32 per CU.  CATGRASP_AMD_FILTER_BLOCKS_PER_CU (dev
 // knob) changes it: with MORE workgroups than the chip holds at once the dispatcher hands evaluations out as slots free up.
 inline long filter_block_cap() {
   static const long per_cu = getenv("CATGRASP_AMD_FILTER_BLOCKS_PER_CU") ? atol(getenv("CATGRASP_AMD_FILTER_BLOCKS_PER_CU")) : 32;
@@ -712,6 +712,42 @@ inline void host_mat4_mul(const float* A, const float* B, float* C) {
   for (int r = 0; r < 4; ++r)
     for (int c = 0; c < 4; ++c)
       C[r * 4 + c] = ((A[r * 4 + 0] * B[0 * 4 + c] + A[r * 4 + 1] * B[1 * 4 + c]) + A[r * 4 + 2] * B[2 * 4 + c]) + A[r * 4 + 3] * B[3 * 4 + c];
+}
+
+// The collision stage of both filter paths, after their compose kernel has run.  MULTI: the evaluations of a segment table (segs; the
+// voxel sets and the nudge flag are per segment then, vox / adjust unused); otherwise one call's.  has_open / has_bg: some evaluation
+// meets a non-empty object / background voxel set.
+template <bool MULTI>
+int launch_filter(long E, const float* h_gripper_in_grasp, int adjust, const float* gripper_vertices, const int* gripper_faces,
+                  int n_gripper_faces, const float* enclosed_vertices, const int* enclosed_faces, int n_enclosed_faces,
+                  const cg_mesh_grid* h_open_grid, const cg_mesh_grid* h_enc_grid, Voxels vox_open, Voxels vox_bg, bool has_open, bool has_bg,
+                  const cg_filter_segment* segs, int n_segs, float resolution, signed char* codes, float* poses_out, signed char* nudge,
+                  int keep_rejected_pose, unsigned long long* work_stats, hipStream_t st) {
+  FilterArgs a;
+  a.E = E;
+  a.gripper_in_grasp = load_mat(h_gripper_in_grasp);
+  a.adjust = adjust;
+  a.mesh[0] = make_mesh(gripper_vertices, gripper_faces, n_gripper_faces, h_open_grid);
+  a.mesh[1] = make_mesh(enclosed_vertices, enclosed_faces, n_enclosed_faces, h_enc_grid);
+  a.vox[0] = vox_open; a.vox[1] = vox_bg;
+  a.res = resolution; a.codes = codes; a.poses_out = poses_out; a.nudge = nudge;
+  a.keep_rejected_pose = keep_rejected_pose; a.work_stats = work_stats;
+  a.segs = segs; a.n_segs = n_segs;
+  long blocks = (E + WAVES - 1) / WAVES;
+  if (blocks > filter_block_cap()) blocks = filter_block_cap();      // grid-stride: 32 blocks per CU
+  // Meshes that collide with anything (non-empty mesh against a non-empty voxel set) must all carry a grid for the grid kernel;
+  // evaluations it cannot cover (a pose outside a grid's validity) come back CODE_PENDING and the exhaustive kernel, which skips
+  // everything else, finishes them.  Without grids the exhaustive kernel does all of it.
+  bool grids = true;
+  if (a.mesh[0].nf > 0 && has_open && !a.mesh[0].has_grid) grids = false;
+  if (a.mesh[1].nf > 0 && has_bg && !a.mesh[1].has_grid) grids = false;
+  a.only_pending = 0;
+  if (grids) {
+    hipLaunchKernelGGL((filter_grasp_pose_kernel<true, MULTI>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
+    a.only_pending = 1;
+  }
+  hipLaunchKernelGGL((filter_grasp_pose_kernel<false, MULTI>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
+  return cg_hip_status(hipGetLastError());
 }
 
 }  // namespace
@@ -752,30 +788,10 @@ extern "C" int cg_filter_grasp_pose_accel(const float* grasp_poses, int n_pose, 
   c.codes = codes; c.poses_out = poses_out; c.nudge = nudge; c.ee_out = ee_in_base_out;
   hipLaunchKernelGGL(compose_grasp_pose_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, c);
   if (ee_in_base_out) return cg_hip_status(hipGetLastError());
-  FilterArgs a;
-  a.E = E;
-  a.gripper_in_grasp = load_mat(h_gripper_in_grasp);
-  a.adjust = adjust_collision_pose;
-  a.mesh[0] = make_mesh(gripper_vertices, gripper_faces, n_gripper_faces, h_open_grid);
-  a.mesh[1] = make_mesh(enclosed_vertices, enclosed_faces, n_enclosed_faces, h_enc_grid);
-  a.vox[0] = Voxels{open_keys, n_open_keys, open_blocks}; a.vox[1] = Voxels{bg_keys, n_bg_keys, bg_blocks};
-  a.res = resolution; a.codes = codes; a.poses_out = poses_out; a.nudge = nudge;
-  a.keep_rejected_pose = keep_rejected_pose; a.work_stats = work_stats;
-  long blocks = (E + WAVES - 1) / WAVES;
-  if (blocks > filter_block_cap()) blocks = filter_block_cap();      // grid-stride: 16 blocks per CU
-  // Meshes that collide with anything (non-empty mesh against a non-empty voxel set) must all carry a grid for the grid kernel;
-  // evaluations it cannot cover (a pose outside a grid's validity) come back CODE_PENDING and the exhaustive kernel, which skips
-  // everything else, finishes them.  Without grids the exhaustive kernel does all of it.
-  bool grids = true;
-  for (int m = 0; m < 2; ++m)
-    if (a.mesh[m].nf > 0 && a.vox[m].nk > 0 && !a.mesh[m].has_grid) grids = false;
-  a.only_pending = 0;
-  if (grids) {
-    hipLaunchKernelGGL((filter_grasp_pose_kernel<true, false>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
-    a.only_pending = 1;
-  }
-  hipLaunchKernelGGL((filter_grasp_pose_kernel<false, false>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
-  return cg_hip_status(hipGetLastError());
+  return launch_filter<false>(E, h_gripper_in_grasp, adjust_collision_pose, gripper_vertices, gripper_faces, n_gripper_faces, enclosed_vertices,
+                              enclosed_faces, n_enclosed_faces, h_open_grid, h_enc_grid, Voxels{open_keys, n_open_keys, open_blocks},
+                              Voxels{bg_keys, n_bg_keys, bg_blocks}, n_open_keys > 0, n_bg_keys > 0, nullptr, 0, resolution, codes, poses_out,
+                              nudge, keep_rejected_pose, work_stats, st);
 }
 
 // ---- several filterGraspPose calls in ONE launch sequence ------------------------------------------------------------------------------
@@ -846,28 +862,9 @@ int filter_multi(const cg_filter_segment* h_segments, const cg_filter_segment* d
   } else {
     hipLaunchKernelGGL(compose_grasp_pose_multi_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, c);
   }
-  FilterArgs a;
-  a.E = E;
-  a.gripper_in_grasp = load_mat(h_gripper_in_grasp);
-  a.adjust = 0;
-  a.mesh[0] = make_mesh(gripper_vertices, gripper_faces, n_gripper_faces, h_open_grid);
-  a.mesh[1] = make_mesh(enclosed_vertices, enclosed_faces, n_enclosed_faces, h_enc_grid);
-  a.vox[0] = Voxels{nullptr, 0, nullptr}; a.vox[1] = Voxels{nullptr, 0, nullptr};
-  a.res = resolution; a.codes = codes; a.poses_out = poses_out; a.nudge = nudge;
-  a.keep_rejected_pose = keep_rejected_pose; a.work_stats = work_stats;
-  a.segs = d_segments; a.n_segs = n_segments;
-  long blocks = (E + WAVES - 1) / WAVES;
-  if (blocks > filter_block_cap()) blocks = filter_block_cap();
-  bool grids = true;
-  if (a.mesh[0].nf > 0 && any_open && !a.mesh[0].has_grid) grids = false;
-  if (a.mesh[1].nf > 0 && any_bg && !a.mesh[1].has_grid) grids = false;
-  a.only_pending = 0;
-  if (grids) {
-    hipLaunchKernelGGL((filter_grasp_pose_kernel<true, true>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
-    a.only_pending = 1;
-  }
-  hipLaunchKernelGGL((filter_grasp_pose_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * WAVES), 0, st, a);
-  return cg_hip_status(hipGetLastError());
+  return launch_filter<true>(E, h_gripper_in_grasp, 0, gripper_vertices, gripper_faces, n_gripper_faces, enclosed_vertices, enclosed_faces,
+                             n_enclosed_faces, h_open_grid, h_enc_grid, Voxels{nullptr, 0, nullptr}, Voxels{nullptr, 0, nullptr}, any_open, any_bg,
+                             d_segments, n_segments, resolution, codes, poses_out, nudge, keep_rejected_pose, work_stats, st);
 }
 
 }  // namespace

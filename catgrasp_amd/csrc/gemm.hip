@@ -98,8 +98,7 @@ __global__ __launch_bounds__(256) void gemm_bias_act_kernel(GemmArgs a) {
   if (!active) return;
   const int col = nb * 32 + l31;
   if (col >= a.N) return;
-  float bias = a.bias ? a.bias[col] : 0.f;
-  if (a.eye_k > 0 && (col % (a.eye_k + 1)) == 0) bias += 1.f;   // flattened identity: col = i*k + i
+  const float bias = cg_gemm_col_bias(a, col);
   if (a.gmax_rows > 0) { gemm_fold_groupmax(a, c0, row0, col, bias, lane); gemm_fold_groupmax(a, c1, row0 + 32, col, bias, lane); return; }
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
@@ -172,8 +171,7 @@ __global__ __launch_bounds__(256) void gemm_bias_act_small_kernel(GemmArgs a) {
   }
   const int col = nb * 32 + l31;
   if (col >= a.N) return;
-  float bias = a.bias ? a.bias[col] : 0.f;
-  if (a.eye_k > 0 && (col % (a.eye_k + 1)) == 0) bias += 1.f;
+  const float bias = cg_gemm_col_bias(a, col);
   if (a.gmax_rows > 0) { gemm_fold_groupmax(a, c, tm * 32, col, bias, lane); return; }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -207,11 +205,8 @@ int launch_gemm(GemmArgs& a, void* stream) {
 extern "C" int cg_gemm_bias_act(const float* x, int M, int K, int ldx, const float* w_packed, int N,
                                 const float* bias, const float* row_bias, int rows_per_group, int ld_rb,
                                 int relu, int eye_k, float* y, int ldy, void* stream) {
-  if (!x || !w_packed || !y) return CG_ERR_ARG;
-  if (M < 0 || N <= 0 || K <= 0 || (K % 8) != 0 || (ldx % 4) != 0 || ldx < K || ldy < N) return CG_ERR_ARG;
-  if (((uintptr_t)x & 15) != 0) return CG_ERR_ARG;
-  if (row_bias && (rows_per_group <= 0 || ld_rb < N)) return CG_ERR_ARG;
-  if (M == 0) return CG_OK;
+  const int bad = cg_gemm_check_args(x, M, K, ldx, w_packed, N, row_bias, rows_per_group, ld_rb, y, ldy, 8);
+  if (bad || M == 0) return bad;
   GemmArgs a{x, M, K, ldx, w_packed, N, (N + 31) / 32, bias, row_bias, rows_per_group, ld_rb, relu, eye_k, y, ldy, 0};
   return launch_gemm(a, stream);
 }

@@ -98,8 +98,7 @@ __global__ __launch_bounds__(256) void gemm_bias_act_split_kernel(GemmArgsB a) {
   if (!active) return;
   const int col = nb * 32 + l31;
   if (col >= a.N) return;
-  float bias = a.bias ? a.bias[col] : 0.f;
-  if (a.eye_k > 0 && (col % (a.eye_k + 1)) == 0) bias += 1.f;   // flattened identity: col = i*k + i
+  const float bias = cg_gemm_col_bias(a, col);
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt) {
 #pragma unroll
@@ -121,11 +120,8 @@ template <bool F16>
 static int gemm_bias_act_split(const float* x, int M, int K, int ldx, const unsigned short* w_split, int N,
                                 const float* bias, const float* row_bias, int rows_per_group, int ld_rb,
                                 int relu, int eye_k, float* y, int ldy, int* status, void* stream) {
-  if (!x || !w_split || !y) return CG_ERR_ARG;
-  if (M < 0 || N <= 0 || K <= 0 || (K % 16) != 0 || (ldx % 4) != 0 || ldx < K || ldy < N) return CG_ERR_ARG;
-  if (((uintptr_t)x & 15) != 0) return CG_ERR_ARG;
-  if (row_bias && (rows_per_group <= 0 || ld_rb < N)) return CG_ERR_ARG;
-  if (M == 0) return CG_OK;
+  const int bad = cg_gemm_check_args(x, M, K, ldx, w_split, N, row_bias, rows_per_group, ld_rb, y, ldy, 16);
+  if (bad || M == 0) return bad;
   GemmArgsB a{x, M, K, ldx, w_split, N, (N + 31) / 32, bias, row_bias, rows_per_group, ld_rb, relu, eye_k, y, ldy, F16 ? status : nullptr};
   dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((a.nblocks + 3) / 4)), block(256);
   hipLaunchKernelGGL(gemm_bias_act_split_kernel<F16>, grid, block, 0, (hipStream_t)stream, a);

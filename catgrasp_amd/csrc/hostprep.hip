@@ -56,64 +56,18 @@ struct Stream {
   }
 };
 
-// One lane per output row.  n_valid >= n_pts: the row's permutation array lives in LDS as u16, rows interleaved
-// (element k of row r at [k*R + r]) so the lanes' sequential initialisation is conflict-free and their random accesses
-// spread over the banks; n_pts steps of Fisher-Yates give a uniform n_pts-subset in uniform order, which is what
-// np.random.choice(replace=False) returns.  Outputs leave in 16-byte groups per lane.
-__global__ __launch_bounds__(64) void draw_ids_perm_kernel(int n_valid, int n_pts, long count, unsigned k0, unsigned k1,
-                                                           int base, int R, long row_offset, int* __restrict__ out) {
-  extern __shared__ unsigned short perm[];
-  const int r = threadIdx.x;
-  const long row = (long)blockIdx.x * R + r;
-  if (r >= R || row >= count) return;
-  for (int k = 0; k < n_valid; ++k) perm[k * R + r] = (unsigned short)k;
-  const long grow = row + row_offset;          // the stream is a function of the GLOBAL row: a shard draws what the whole would
-  const unsigned c0 = (unsigned)grow, c2 = (unsigned)(grow >> 32);
-  int* o = out + row * n_pts;
-  const bool vec = ((n_pts & 3) == 0) && (((uintptr_t)out & 15) == 0);
-  // 16 steps per batch: their random words do not depend on the permutation, so the four Philox blocks of a batch are
-  // independent chains (instruction-level parallelism) instead of sitting inside the swap chain, and the swap chain itself is
-  // only the LDS read -> write of one step (LDS operations of a wave execute in order).  j = i + floor(u * (n - i) / 2^32): the
-  // multiply-shift map without rejection (bias <= n / 2^32 < 1e-6 relative).
-  for (int i0 = 0; i0 < n_pts; i0 += 16) {
-    U4 rb[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rb[q] = philox4x32_10(U4{c0, (unsigned)(i0 >> 2) + q, c2, 0u}, k0, k1);
-    int q4[4];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const int i = i0 + t;
-      if (i < n_pts) {
-        const U4& w = rb[t >> 2];
-        const unsigned u = ((t & 3) == 0) ? w.x : ((t & 3) == 1) ? w.y : ((t & 3) == 2) ? w.z : w.w;
-        const int j = i + (int)__umulhi(u, (unsigned)(n_valid - i));
-        const unsigned short pa = perm[i * R + r], pb = perm[j * R + r];
-        perm[j * R + r] = pa;               // a[i] itself is never read again
-        const int v = (int)pb + base;
-        if (vec) {
-          q4[t & 3] = v;
-          if ((t & 3) == 3) *(int4*)(o + i - 3) = make_int4(q4[0], q4[1], q4[2], q4[3]);
-        } else {
-          o[i] = v;
-        }
-      }
-    }
-  }
-}
-
-// The same draw as a SORT: one workgroup per row.  Every point index gets a 48-bit random key (two Philox words; a tie between two of
-// 2,500 keys has probability 1e-8 per row and is then decided by the index), the (key, index) pairs are bitonic-sorted and the first
-// n_pts indices are the row: a uniform n_pts-subset in uniform order, like np.random.choice(replace=False).  The Fisher-Yates kernel
-// above runs ONE LANE per row down a chain of n_pts dependent LDS swaps: ~250 us for a row however few rows there are (a quarter of a
-// one-pose predict_batch call).  Here a row is N = 2^LOG_N pairs on 256 threads, E = N / 256 per thread IN REGISTERS: a
+// Draws without replacement from at most 1,024 points, as a SORT: one workgroup per row.  Every point index gets a 48-bit random key
+// (two Philox words; a tie between two of 1,024 keys has probability 2e-9 per row and is then decided by the index), the (key, index)
+// pairs are bitonic-sorted and the first n_pts indices are the row: a uniform n_pts-subset in uniform order, like
+// np.random.choice(replace=False).  A row is N = 2^LOG_N = 1,024 pairs on 256 threads, E = N / 256 = 4 per thread IN REGISTERS: a
 // compare-exchange round with partner distance 2^p runs inside the registers of a thread whenever bit p of the element index is one of
 // the thread's register bits, and the elements are re-dealt through LDS (write E, barrier, read E) only when the next round's bit is
-// not -- three deals per merge stage instead of a trip through LDS per round (78 rounds at N = 4096: the first version of this kernel,
-// 1.77 ms per 6,250 rows against 0.84 for the Fisher-Yates kernel it replaced).
+// not -- a few deals per merge stage instead of a trip through LDS per round.  (Larger clouds take the bijection kernel below; the
+// Fisher-Yates and wider sort kernels it replaced are measured in DESIGN 4.4 / 4.7.)
 template <int LOG_N>
 struct SortGeo {
   static constexpr int LOG_T = 8, LOG_E = LOG_N - LOG_T, E = 1 << LOG_E, N = 1 << LOG_N;
-  static_assert(LOG_E >= 2 && LOG_E <= 5, "2,048 .. 8,192 ... pairs per row on 256 threads");
+  static_assert(LOG_N == 10, "1,024 pairs per row on 256 threads: the one size cg_draw_resample_ids launches");
   // lowest register bit of the layout that holds element-index bit p in a thread's registers
   static constexpr int lo_of(int p) { return (p / LOG_E) * LOG_E > LOG_N - LOG_E ? LOG_N - LOG_E : (p / LOG_E) * LOG_E; }
 };
@@ -252,8 +206,9 @@ __global__ __launch_bounds__(256) void draw_ids_bijection_kernel(int n_valid, in
 
 // The swap chain of numpy's permutation(n_valid) for `count` rows whose swap partners the host extracted from numpy's generator
 // (cg_host_numpy_shuffle_partners): a[i] <-> a[j(i)] for i = n_valid-1 .. 1 on a = arange(n_valid), out = a[:n_pts] + base.
-// One lane per row, the row's array in LDS as u16, rows interleaved like draw_ids_perm_kernel (the LDS operations of a lane
-// execute in program order, so the chain needs no other synchronisation); partners arrive 8 steps per 16-byte load, one load
+// One lane per row, the row's array in LDS as u16, rows interleaved (element k of row r at [k*R + r]: the lanes' sequential
+// initialisation is conflict-free and their random accesses spread over the banks; the LDS operations of a lane execute in
+// program order, so the chain needs no other synchronisation); partners arrive 8 steps per 16-byte load, one load
 // ahead of the chain; the finished rows leave through coalesced stores by the whole wave.
 __global__ __launch_bounds__(64) void apply_shuffle_rows_kernel(const unsigned short* __restrict__ partners, long row_stride,
                                                                 int n_valid, int n_pts, long count, int base, int R,
@@ -292,7 +247,7 @@ __global__ __launch_bounds__(64) void apply_shuffle_rows_kernel(const unsigned s
   }
 }
 
-// n_valid < n_pts (or a cloud too large for the LDS permutation): iid uniform indices = np.random.choice(replace=True)
+// n_valid < n_pts: iid uniform indices = np.random.choice(replace=True)
 __global__ __launch_bounds__(256) void draw_ids_iid_kernel(int n_valid, int n_pts, long count, unsigned k0, unsigned k1,
                                                            int base, long row_offset, int* __restrict__ out) {
   const long total = count * n_pts;
@@ -413,8 +368,7 @@ extern "C" int cg_draw_resample_ids(int n_valid, int n_pts, long count, unsigned
   if (!out) return CG_ERR_ARG;
   const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
   hipStream_t s = (hipStream_t)stream;
-  static const bool use_sort = getenv("CATGRASP_AMD_DRAW_SORT") && getenv("CATGRASP_AMD_DRAW_SORT")[0] == '1';     // dev knob: the round-4/5 kernels
-  if (n_valid >= n_pts && n_valid > 1024 && !use_sort) {   // without replacement: the keyed bijection (halves of >= 6 bits), any cloud size
+  if (n_valid >= n_pts && n_valid > 1024) {   // without replacement: the keyed bijection (halves of >= 6 bits), any cloud size up to 2^30
     int bits = 2;
     while (bits < 30 && (1L << bits) < (long)n_valid) bits += 2;
     if ((1L << bits) < (long)n_valid) return CG_ERR_UNSUPPORTED;
@@ -422,30 +376,10 @@ extern "C" int cg_draw_resample_ids(int n_valid, int n_pts, long count, unsigned
     hipLaunchKernelGGL(draw_ids_bijection_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, bits / 2, out);
     return cg_hip_status(hipGetLastError());
   }
-  if (n_valid >= n_pts && n_valid <= 8192) {             // (key, index) pairs of the whole cloud fit 64 KB of LDS: the sort kernel
-    const dim3 grid((unsigned)count), block(256);
-    if (n_valid <= 1024) hipLaunchKernelGGL(draw_ids_sort_kernel<10>, grid, block, 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, out);
-    else if (n_valid <= 2048) hipLaunchKernelGGL(draw_ids_sort_kernel<11>, grid, block, 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, out);
-    else if (n_valid <= 4096) hipLaunchKernelGGL(draw_ids_sort_kernel<12>, grid, block, 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, out);
-    else hipLaunchKernelGGL(draw_ids_sort_kernel<13>, grid, block, 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, out);
+  if (n_valid >= n_pts) {                     // at most 1,024 points: the sort kernel
+    hipLaunchKernelGGL(draw_ids_sort_kernel<10>, dim3((unsigned)count), dim3(256), 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, out);
     return cg_hip_status(hipGetLastError());
   }
-  if (n_valid >= n_pts && n_valid <= 65535) {
-    constexpr size_t LDS = 128 * 1024;
-    int R = (int)(LDS / ((size_t)n_valid * 2));
-    if (R > 64) R = 64;
-    if (R >= 1) {
-      const size_t bytes = (size_t)R * n_valid * 2;
-      auto kern = draw_ids_perm_kernel;
-      if (bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        if (e != hipSuccess) return (int)e;
-      }
-      hipLaunchKernelGGL(kern, dim3((unsigned)((count + R - 1) / R)), dim3(64), bytes, s, n_valid, n_pts, count, k0, k1, base, R, row_offset, out);
-      return cg_hip_status(hipGetLastError());
-    }
-  }
-  if (n_valid >= n_pts) return CG_ERR_UNSUPPORTED;       // without replacement from > 65535 points: not on this path
   if ((n_pts & 3) != 0) return CG_ERR_UNSUPPORTED;
   const long total = count * n_pts;
   hipLaunchKernelGGL(draw_ids_iid_kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, s, n_valid, n_pts, count, k0, k1, base, row_offset, out);
@@ -462,12 +396,13 @@ extern "C" int cg_apply_shuffle_rows(const unsigned short* partners, long row_st
   int R = (int)(LDS / ((size_t)n_valid * 2));
   if (R > 64) R = 64;
   const size_t bytes = (size_t)R * n_valid * 2;
-  auto kern = apply_shuffle_rows_kernel;
   if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-    if (e != hipSuccess) return (int)e;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return CG_ERR_UNSUPPORTED;
+    const int st = cg_allow_dynamic_lds<apply_shuffle_rows_kernel>(dev, LDS);
+    if (st != CG_OK) return st;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)((count + R - 1) / R)), dim3(64), bytes, (hipStream_t)stream, partners, row_stride, n_valid,
+  hipLaunchKernelGGL(apply_shuffle_rows_kernel, dim3((unsigned)((count + R - 1) / R)), dim3(64), bytes, (hipStream_t)stream, partners, row_stride, n_valid,
                      n_pts, count, base, R, out);
   return cg_hip_status(hipGetLastError());
 }

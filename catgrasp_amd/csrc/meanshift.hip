@@ -111,13 +111,9 @@ int launch_climb(const void* pts, int n, const double* seeds, long n_seeds, doub
   long blocks = (n_seeds + wpb - 1) / wpb;
   const double bw2 = bandwidth * bandwidth, stop = 1e-3 * bandwidth;
   if (lds) {
-    auto kern = meanshift_climb_kernel<T, true>;
-    static bool attr_set[CG_MAX_DEVICES] = {};
-    if (!attr_set[dev]) {
-      e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, MS_LDS_BYTES);
-      if (e != hipSuccess) return (int)e;
-      attr_set[dev] = true;
-    }
+    constexpr auto kern = meanshift_climb_kernel<T, true>;
+    const int st = cg_allow_dynamic_lds<kern>(dev, MS_LDS_BYTES);
+    if (st != CG_OK) return st;
     if (blocks > n_cu) blocks = n_cu;                       // one workgroup holds a CU's LDS: stage once, stride over the seeds
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(MS_CLIMB_THREADS), (size_t)n * 3 * sizeof(T), stream, (const T*)pts, n, seeds,
                        n_seeds, bw2, stop, max_iter, means, counts, iters);

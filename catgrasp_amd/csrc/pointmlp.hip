@@ -277,6 +277,24 @@ __global__ void fill_kernel(float* p, size_t n, float v) {
 
 }  // namespace
 
+// the launch plan of this file's and pointmlp_split.hip's entry points: see cg_common.hpp
+CgPointMlpPlan cg_pointmlp_plan(int B, int ntiles, int nsplit, int slots_per_cu, int min_tiles, int tail_split, float* out, hipStream_t s) {
+  CgPointMlpPlan p{CG_ERR_UNSUPPORTED, 0, nsplit < 1 ? 1 : nsplit > ntiles ? ntiles : nsplit, B, 1};
+  if (hipGetDevice(&p.dev) != hipSuccess) return p;
+  if (p.nsplit == 1 && ntiles >= min_tiles) {
+    const int slots = slots_per_cu * cg_device_cu_count(p.dev);
+    if (slots <= 0) return p;
+    if (B >= slots && (B % slots) != 0) { p.n_main = B - B % slots; p.tail_split = tail_split; }
+  }
+  if (p.nsplit > 1 || p.tail_split > 1) {
+    const int first = (p.nsplit > 1) ? 0 : p.n_main;
+    const size_t n = (size_t)(B - first) * 1024;
+    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out + (size_t)first * 1024, n, -INFINITY);
+  }
+  p.status = CG_OK;
+  return p;
+}
+
 extern "C" int cg_pointmlp_max(const float* x, int B, int N, const float* t3, const float* w1, const float* b1,
                                int mid_mode, const float* wm_packed, const float* bm, const float* t64,
                                const float* w2_packed, const float* b2, const float* w3_packed, const float* b3,
@@ -287,46 +305,28 @@ extern "C" int cg_pointmlp_max(const float* x, int B, int N, const float* t3, co
   if (mid_mode == 2 && !t64) return CG_ERR_ARG;
   if (pointfeat && mid_mode != 2) return CG_ERR_ARG;
   if (B == 0) return CG_OK;
-  const int ntiles = (N + TP - 1) / TP;
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > ntiles) nsplit = ntiles;
   hipStream_t s = (hipStream_t)stream;
-  // Tail balancing (as in pointmlp_split.hip): with one workgroup per sample and B >= the number of resident workgroups
-  // (2 per CU), the samples of the last, partially filled scheduling round are split 8 ways so that round is short.
-  int n_main = B, tail_split = 1;
-  if (nsplit == 1 && ntiles >= 8) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return CG_ERR_UNSUPPORTED;
-    const int slots = 2 * cg_device_cu_count(dev);          // resident workgroups (57 KB of LDS each): two per CU
-    if (slots <= 0) return CG_ERR_UNSUPPORTED;
-    if (B >= slots && (B % slots) != 0) { n_main = B - B % slots; tail_split = 8; }
-  }
-  if (nsplit > 1 || tail_split > 1) {
-    const int first = (nsplit > 1) ? 0 : n_main;
-    const size_t n = (size_t)(B - first) * 1024;
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out + (size_t)first * 1024, n, -INFINITY);
-  }
+  // two resident workgroups per CU (73,728 B of LDS each); the tail is balanced from 8 tiles on, split 8 ways
+  const CgPointMlpPlan plan = cg_pointmlp_plan(B, (N + TP - 1) / TP, nsplit, 2, 8, 8, out, s);
+  if (plan.status != CG_OK) return plan.status;
+  nsplit = plan.nsplit;
+  const int n_main = plan.n_main, tail_split = plan.tail_split;
   Args a{x, B, N, t3, w1, b1, wm_packed, bm, t64, w2_packed, b2, w3_packed, b3, relu3, nsplit, n_main, tail_split, out, pointfeat};
   const size_t lds = LDS_FLOATS * sizeof(float);          // 73,728 B: above the 64 KB default limit -> per-device function attribute
-  int dev_l = 0;
-  if (hipGetDevice(&dev_l) != hipSuccess || dev_l < 0 || dev_l >= CG_MAX_DEVICES) return CG_ERR_UNSUPPORTED;
   // few workgroups (a call of a few poses): divide the last layer's channels over 2 / 4 / 8 workgroups per (sample, slice)
   const long wgs = (long)n_main * nsplit + (long)(B - n_main) * tail_split;
   int csi = tail_split > 1 ? 0 : wgs <= 64 ? 3 : wgs <= 128 ? 2 : wgs <= 256 ? 1 : 0;
   static const char* cs_env = getenv("CATGRASP_AMD_POINTMLP_CSPLIT");     // dev knob: 1 / 2 / 4 / 8
   if (cs_env) { const int v = atoi(cs_env); csi = tail_split > 1 ? 0 : v == 8 ? 3 : v == 4 ? 2 : v == 2 ? 1 : 0; }
-  static bool attr_set[3][4][CG_MAX_DEVICES] = {};
+  static bool lds_allowed[3][4][CG_MAX_DEVICES] = {};
   typedef void (*kern_t)(Args);
   static const kern_t kerns[3][4] = {
       {pointmlp_max_kernel<0, 1>, pointmlp_max_kernel<0, 2>, pointmlp_max_kernel<0, 4>, pointmlp_max_kernel<0, 8>},
       {pointmlp_max_kernel<1, 1>, pointmlp_max_kernel<1, 2>, pointmlp_max_kernel<1, 4>, pointmlp_max_kernel<1, 8>},
       {pointmlp_max_kernel<2, 1>, pointmlp_max_kernel<2, 2>, pointmlp_max_kernel<2, 4>, pointmlp_max_kernel<2, 8>}};
   const kern_t kern = kerns[mid_mode][csi];
-  if (!attr_set[mid_mode][csi][dev_l]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set[mid_mode][csi][dev_l] = true;
-  }
+  const int st = cg_allow_dynamic_lds((const void*)kern, plan.dev, lds, lds_allowed[mid_mode][csi]);
+  if (st != CG_OK) return st;
   dim3 grid((unsigned)(wgs << csi)), block(256);
   hipLaunchKernelGGL(kern, grid, block, lds, s, a);
   return cg_hip_status(hipGetLastError());

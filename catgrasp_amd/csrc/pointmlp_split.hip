@@ -430,23 +430,13 @@ __global__ __launch_bounds__(64 * RT, 2) void pointmlp_max_split_kernel(ArgsB a)
   }
 }
 
-__global__ void fill_kernel_b(float* p, size_t n, float v) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
-
 template <int MID, int RT, bool F16, bool MX = false>
 int launch(const ArgsB& a, hipStream_t s, int dev) {
   constexpr int NT = Geo<RT>::NT;
   constexpr size_t LDS_BYTES = Geo<RT, MX>::LDS_BYTES;
-  auto kern = pointmlp_max_split_kernel<MID, RT, F16, MX>;
-  static bool attr_set[CG_MAX_DEVICES] = {};     // per instantiation and per device (the attribute is per device)
-  if (dev < 0 || dev >= CG_MAX_DEVICES) return CG_ERR_UNSUPPORTED;
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = pointmlp_max_split_kernel<MID, RT, F16, MX>;
+  const int st = cg_allow_dynamic_lds<kern>(dev, LDS_BYTES);
+  if (st != CG_OK) return st;
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.n_main * a.nsplit + (a.B - a.n_main) * a.tail_split)), dim3(NT), LDS_BYTES, s, a);
   return cg_hip_status(hipGetLastError());
 }
@@ -467,29 +457,14 @@ static int pointmlp_max_split(const float* x, int B, int N, const float* t3, con
   if (mid_mode == 2 && !t64) return CG_ERR_ARG;
   if (pointfeat && mid_mode != 2) return CG_ERR_ARG;
   const int ntiles = (N + tile_points - 1) / tile_points;
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > ntiles) nsplit = ntiles;
   hipStream_t s = (hipStream_t)stream;
-  // Tail balancing: with one workgroup per sample (nsplit == 1) and B >= #CU, the last B % #CU samples would occupy a few CUs
-  // for a whole sample's duration while the rest of the chip idles; they are split one workgroup per tile instead (atomic max
-  // into a -inf pre-filled row), so the final round lasts one tile, not ntiles.
-  int n_main = B, tail_split = 1;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return CG_ERR_UNSUPPORTED;
-  if (nsplit == 1 && ntiles > 1) {
-    const int n_cu = cg_device_cu_count(dev);
-    if (n_cu <= 0) return CG_ERR_UNSUPPORTED;
-    if (B >= n_cu && (B % n_cu) != 0) { n_main = B - B % n_cu; tail_split = ntiles; }
-  }
-  if (nsplit > 1 || tail_split > 1) {
-    const int first = (nsplit > 1) ? 0 : n_main;
-    const size_t n = (size_t)(B - first) * 1024;
-    hipLaunchKernelGGL(fill_kernel_b, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out + (size_t)first * 1024, n, -INFINITY);
-  }
-  ArgsB a{x, B, N, t3, w1, b1, wm_split, bm, t64, w2_split, b2, w3_split, b3, relu3, nsplit, n_main, tail_split, out, pointfeat, F16 ? status : nullptr};
-  if (mid_mode == 0) return launch<0, 8, F16, MX>(a, s, dev);
-  if (mid_mode == 1) return launch<1, 8, F16, MX>(a, s, dev);
-  return launch<2, 8, F16, MX>(a, s, dev);
+  // one resident workgroup per CU; the tail is balanced from 2 tiles on, one workgroup per tile: its round lasts one tile, not ntiles
+  const CgPointMlpPlan plan = cg_pointmlp_plan(B, ntiles, nsplit, 1, 2, ntiles, out, s);
+  if (plan.status != CG_OK) return plan.status;
+  ArgsB a{x, B, N, t3, w1, b1, wm_split, bm, t64, w2_split, b2, w3_split, b3, relu3, plan.nsplit, plan.n_main, plan.tail_split, out, pointfeat, F16 ? status : nullptr};
+  if (mid_mode == 0) return launch<0, 8, F16, MX>(a, s, plan.dev);
+  if (mid_mode == 1) return launch<1, 8, F16, MX>(a, s, plan.dev);
+  return launch<2, 8, F16, MX>(a, s, plan.dev);
 }
 
 extern "C" int cg_pointmlp_max_bf16x3(const float* x, int B, int N, const float* t3, const float* w1, const float* b1,

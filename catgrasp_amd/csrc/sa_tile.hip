@@ -392,13 +392,9 @@ __global__ void sa_concat_kernel(const float* xyz, const float* points, long row
 
 template <int KP, bool WIDE, int TR>
 int launch_st(const STArgs& a, size_t lds, long nslots, int dev, hipStream_t s) {
-  auto kern = sa_tile_kernel<KP, WIDE, TR>;
-  static bool attr_set[CG_MAX_DEVICES] = {};
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = sa_tile_kernel<KP, WIDE, TR>;
+  const int st = cg_allow_dynamic_lds<kern>(dev, 160 * 1024);
+  if (st != CG_OK) return st;
   const int n_cu = cg_device_cu_count(dev);
   if (n_cu <= 0) return CG_ERR_UNSUPPORTED;
   int per_cu = (int)((160 * 1024) / lds);

@@ -592,13 +592,9 @@ int launch_sa_reg(SAArgs& a, hipStream_t s, int dev) {
   }
   long grid = (nslots + waves - 1) / waves;
   if (grid > n_cu) grid = n_cu;
-  auto kern = sa_reg_kernel<N0, N1, N2, PACK, NT>;
-  static bool attr_set[CG_MAX_DEVICES] = {};
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = sa_reg_kernel<N0, N1, N2, PACK, NT>;
+  const int st = cg_allow_dynamic_lds<kern>(dev, 160 * 1024);
+  if (st != CG_OK) return st;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), lds, s, a);
   return cg_hip_status(hipGetLastError());
 }
@@ -677,14 +673,9 @@ int launch_sa(SAArgs& a, int cs, hipStream_t s, int dev) {
   if (wg_per_cu < 1) wg_per_cu = 1;
   long grid = (nslots + waves - 1) / waves;
   if (grid > (long)n_cu * wg_per_cu) grid = (long)n_cu * wg_per_cu;              // persistent: the waves loop over the slots
-  auto kern = sa_group_mlp_max_kernel<MAXNB, PACK>;
-  static bool attr_set[CG_MAX_DEVICES] = {};
-  if (dev < 0 || dev >= CG_MAX_DEVICES) return CG_ERR_UNSUPPORTED;
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = sa_group_mlp_max_kernel<MAXNB, PACK>;
+  const int st = cg_allow_dynamic_lds<kern>(dev, 160 * 1024);
+  if (st != CG_OK) return st;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), lds, s, a, cs, waves);
   return cg_hip_status(hipGetLastError());
 }

@@ -202,7 +202,7 @@ def draw_ids_device(n_valid, n_pts, count, device, generator=None, seed=None, ba
         out = torch.empty((count, n_pts), dtype=torch.int32, device=device)
     assert out.shape == (count, n_pts) and out.dtype == torch.int32 and out.is_contiguous() and out.is_cuda
     st = L.lib().cg_draw_resample_ids(n_valid, n_pts, count, seed & (2 ** 64 - 1), base, row_offset, L._p(out), L._stream())
-    if st == -2:        # CG_ERR_UNSUPPORTED: a shape outside the kernel's (without replacement from > 65535 points; n_pts % 4 != 0)
+    if st == -2:        # CG_ERR_UNSUPPORTED: a shape outside the kernel's (without replacement from > 2^30 points; with replacement and n_pts % 4 != 0)
         gen = torch.Generator(device=device); gen.manual_seed((seed + 0x9E3779B97F4A7C15 * (row_offset + 1)) % (2 ** 63))
         if n_valid < n_pts:
             out.copy_(torch.randint(0, n_valid, (count, n_pts), device=device, generator=gen, dtype=torch.int32) + base)

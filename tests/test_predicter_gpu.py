@@ -304,6 +304,8 @@ def test_predict_batch_device_rng_and_id_validation(cuda_device):
     assert np.array_equal(whole[25:], part)
     small = transforms.draw_ids_device(700, 512, 20, cuda_device, seed=2).cpu().numpy()        # <= 1,024 points: the sort kernel
     assert all(len(np.unique(r)) == 512 for r in small) and small.max() < 700
+    edge = transforms.draw_ids_device(1024, 1000, 20, cuda_device, seed=2).cpu().numpy()      # the sort kernel's largest cloud; (1025, 1000) above is the bijection's smallest
+    assert all(len(np.unique(r)) == 1000 for r in edge) and edge.min() >= 0 and edge.max() < 1024
     rep = transforms.draw_ids_device(700, 2048, 50, cuda_device, seed=3).cpu().numpy()       # with replacement
     assert rep.min() >= 0 and rep.max() < 700 and rep.shape == (50, 2048)
     ref = tref.predict_batch_post(oref.pointnet_cls_forward(sd, torch.from_numpy(np.stack(
