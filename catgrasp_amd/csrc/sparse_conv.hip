@@ -18,12 +18,18 @@
 // ds_read_b128 services together fall on 16 different bank quadruples.
 #include "cg_common.hpp"
 #include "../../include/catgrasp_amd_sparse.h"
+#include "../../include/catgrasp_amd_pointgroup.h"
 
 namespace {
 
 __device__ __forceinline__ float prologue(float x, float s, float b) { return fmaxf(x * s + b, 0.f); }
 
-__global__ __launch_bounds__(256) void sparse_conv_kernel(const float* __restrict__ feats, long n_in, const int* __restrict__ nbr, long n_out, int K,
+// TWO: the input rows are the concatenation [feats | feats_b] of two matrices with the same row order, cin_a and cin - cin_a
+// channels wide (both multiples of 16): a 16-byte chunk below cin_a is read from feats, the others from feats_b.  Nothing else
+// differs, so every output element is the same fmaf chain as over the concatenated matrix (cg_sparse_conv_cat).
+template <bool TWO>
+__global__ __launch_bounds__(256) void sparse_conv_kernel(const float* __restrict__ feats, const float* __restrict__ feats_b, int cin_a, long n_in,
+                                                          const int* __restrict__ nbr, long n_out, int K,
                                                           const float* __restrict__ weight, const float* __restrict__ bias,
                                                           const float* __restrict__ scale, const float* __restrict__ shift,
                                                           const float* __restrict__ residual, int cin, int cout, float* __restrict__ out) {
@@ -55,6 +61,7 @@ __global__ __launch_bounds__(256) void sparse_conv_kernel(const float* __restric
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (src >= 0) {
         const float* p = feats + (size_t)src * cin + ch * 4;
+        if constexpr (TWO) p = ch * 4 < cin_a ? feats + (size_t)src * cin_a + ch * 4 : feats_b + (size_t)src * (cin - cin_a) + (ch * 4 - cin_a);
         if (vec && ch * 4 + 4 <= cin) {
           v = *(const float4*)p;
           if (scale) {
@@ -141,7 +148,24 @@ extern "C" int cg_sparse_conv(const float* feats, long n_in, const int* nbr, lon
   const int waves = (cout + 31) / 32;                       // 1 .. 4: one per 32 output channels
   const int cp = (cin + 7) & ~7;
   const size_t lds = (size_t)32 * (cp + 4) * sizeof(float);      // at most 29,184 B
-  hipLaunchKernelGGL(sparse_conv_kernel, dim3((unsigned)((n_out + 31) / 32)), dim3(64 * waves), lds, (hipStream_t)stream, feats, n_in, nbr,
-                     n_out, K, weight, bias, scale, shift, residual, cin, cout, out);
+  hipLaunchKernelGGL(sparse_conv_kernel<false>, dim3((unsigned)((n_out + 31) / 32)), dim3(64 * waves), lds, (hipStream_t)stream, feats,
+                     (const float*)nullptr, cin, n_in, nbr, n_out, K, weight, bias, scale, shift, residual, cin, cout, out);
+  return cg_hip_status(hipGetLastError());
+}
+
+// cg_sparse_conv over the row-wise concatenation [feats_a | feats_b], which is never formed (include/catgrasp_amd_pointgroup.h).
+extern "C" int cg_sparse_conv_cat(const float* feats_a, int cin_a, const float* feats_b, int cin_b, long n_in, const int* nbr, long n_out, int K,
+                                  const float* weight, const float* bias, const float* scale, const float* shift, const float* residual,
+                                  int cout, float* out, void* stream) {
+  if (n_in < 0 || n_out < 0 || n_in > (1L << 26) || n_out > (1L << 26) || (K != 1 && K != 8 && K != 27) || cin_a <= 0 || cin_b <= 0 || cout <= 0 ||
+      (scale == nullptr) != (shift == nullptr))
+    return CG_ERR_ARG;
+  if (cin_a % 16 || cin_b % 16 || (long)cin_a + cin_b > CG_SPARSE_MAX_CIN || !cout_ok(cout)) return CG_ERR_UNSUPPORTED;
+  if (n_out == 0) return CG_OK;
+  if (!nbr || !weight || !out || (n_in > 0 && (!feats_a || !feats_b))) return CG_ERR_ARG;
+  const int cin = cin_a + cin_b, waves = (cout + 31) / 32;
+  const size_t lds = (size_t)32 * (cin + 4) * sizeof(float);
+  hipLaunchKernelGGL(sparse_conv_kernel<true>, dim3((unsigned)((n_out + 31) / 32)), dim3(64 * waves), lds, (hipStream_t)stream, feats_a, feats_b,
+                     cin_a, n_in, nbr, n_out, K, weight, bias, scale, shift, residual, cin, cout, out);
   return cg_hip_status(hipGetLastError());
 }

@@ -371,3 +371,12 @@ def objects_from_segmentation(cloud_xyz, cloud_normal, labels, order):
     (run_grasp_simulation.py:266-280: one object per surviving segment id, in that order)."""
     xyz, nrm, labels = np.asarray(cloud_xyz), np.asarray(cloud_normal), np.asarray(labels)
     return [{'ob_pts': xyz[labels == seg_id], 'ob_normals': nrm[labels == seg_id]} for seg_id in order]
+
+
+def objects_from_scene(data, predictor, **select_kw):
+    """Scene cloud -> the object list `evaluate_objects` consumes: `predictor.predict` (a predicter.PointGroupPredictor), then
+    `segmentation.select_segments(**select_kw)` on its labels, then `objects_from_segmentation`."""
+    from . import segmentation
+    labels = predictor.predict(data)
+    cleaned, order = segmentation.select_segments(np.asarray(data['cloud_xyz']), labels, **select_kw)
+    return objects_from_segmentation(data['cloud_xyz'], data['cloud_normal'], cleaned, order)

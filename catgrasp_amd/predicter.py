@@ -1,5 +1,5 @@
-"""Drop-in for the reference's `predicter.GraspPredicter` / `predicter.NunocsPredicter`
-(predicter.py:39-203) on MI355X: same constructor argument, attributes and method results, with the
+"""Drop-in for the reference's `predicter.GraspPredicter` / `predicter.NunocsPredicter` / `predicter.PointGroupPredictor`
+(predicter.py:39-338) on MI355X: same constructor argument, attributes and method results, with the
 per-candidate python transform loop (predicter.py:71-74), the chunk-of-200 forward (predicter.py:76-91)
 and the NUNOCS decode (predicter.py:144-150) replaced by device kernels.
 
@@ -571,3 +571,86 @@ class NunocsPredicter:
         self.best_ratio = best_ratio
         self.nocs_pose = best_transform.copy()
         return nocs_cloud, best_transform
+
+
+class PointGroupPredictor:
+    """Drop-in for the reference's `predicter.PointGroupPredictor` (predicter.py:206-338): scene cloud -> instance label per point.
+    Reads `config_pointgroup.yaml` and `best_val.pth.tar` from `artifact_dir`; without one, from the reference's layout
+    `<root>/artifacts-<id>/` (root: the argument, else artifact_root())."""
+    class_name_to_artifact_id = {'nut': 40, 'hnm': 68, 'screw': 77}          # predicter.py:208-212
+
+    def __init__(self, class_name, artifact_dir=None, root=None, device=None):
+        from . import pointgroup
+        self.class_name = class_name
+        if artifact_dir is None:
+            artifact_dir = f"{artifact_root() if root is None else root}/artifacts-{self.class_name_to_artifact_id[class_name]}"
+            print('PointGroupPredictor artifact_dir', artifact_dir)
+        config_dir, ckpt_dir = f'{artifact_dir}/config_pointgroup.yaml', f'{artifact_dir}/best_val.pth.tar'
+        for path in (config_dir, ckpt_dir):
+            if not os.path.exists(path):
+                raise FileNotFoundError(f'PointGroupPredictor: {path} not found (the artifacts are external downloads; pass artifact_dir, '
+                                        'or root, the directory that holds artifacts-<id>/)')
+        self.cfg_pg = pointgroup.config_from_yaml(config_dir)
+        with open(config_dir, 'r') as ff:
+            self.cfg = yaml.safe_load(ff)
+        self.device = _device(device)
+        self.model = pointgroup.load_model(pointgroup.PointGroup(self.cfg_pg), ckpt_dir)
+        self.model.to(self.device).eval()
+        self.n_slice_per_side = 1
+
+    def front_end(self, data):
+        """predicter.py:234-302 on the device: per slice the keep mask, the voxel down-sampling at cfg['downsample_size'], the nearest
+        original point of every centroid, integer voxel coordinates, then the voxel maps and the voxel features [normal | xyz].
+        -> dict of device tensors: picks (per slice, rows of the slice's points), xyz_original (N,3) f32, normals (N,3) f32,
+        locs (N,4) i64, spatial_shape (numpy), voxel_coords, p2v_map, v2p_map, voxel_feats, batch_offsets."""
+        from . import pointgroup_ops
+        from .aligning import voxel_down_sample_device
+        from .cluster import nearest_center
+        dev = self.device
+        cloud = torch.as_tensor(np.asarray(data['cloud_xyz']), dtype=torch.float64).to(dev)
+        normal = torch.as_tensor(np.asarray(data['cloud_normal']), dtype=torch.float64).to(dev)
+        ns = self.n_slice_per_side
+        xmin, xmax, ymin, ymax = cloud[:, 0].min(), cloud[:, 0].max(), cloud[:, 1].min(), cloud[:, 1].max()
+        xlen, ylen = (xmax - xmin) / ns, (ymax - ymin) / ns
+        batch_offsets, locs, xyz_all, feats, picks = [0], [], [], [], []
+        for ix in range(ns):
+            for iy in range(ns):
+                xstart, ystart = xmin + ix * xlen, ymin + iy * ylen
+                keep = (cloud[:, 0] >= xstart) & (cloud[:, 0] <= xstart + xlen) & (cloud[:, 1] >= ystart) & (cloud[:, 1] <= ystart + ylen)
+                xyz_origin = cloud[keep].contiguous()
+                pts = voxel_down_sample_device(xyz_origin, self.cfg['downsample_size']).contiguous()
+                idx, _ = nearest_center(pts, xyz_origin)                 # cKDTree(xyz_origin).query(pts)
+                xyz_origin = xyz_origin[idx]
+                xyz = xyz_origin * self.cfg_pg.scale
+                xyz = xyz - xyz.min(0).values
+                batch_offsets.append(batch_offsets[-1] + xyz.shape[0])
+                i = ix + iy * ns
+                locs.append(torch.cat([torch.full((xyz.shape[0], 1), i, dtype=torch.int64, device=dev), xyz.long()], 1))
+                xyz_all.append(xyz_origin)
+                feats.append(normal[keep][idx])
+                picks.append(idx)
+        batchsize = len(batch_offsets) - 1
+        locs = torch.cat(locs, 0)
+        coords_float = torch.cat(xyz_all, 0).float()
+        normals = torch.cat(feats, 0).float()
+        spatial_shape = np.clip((locs.max(0).values[1:] + 1).cpu().numpy(), self.cfg_pg.full_scale[0], None)
+        voxel_coords, p2v_map, v2p_map = pointgroup_ops.voxelization_idx(locs, batchsize, self.cfg_pg.mode)
+        point_feats = torch.cat((normals, coords_float), 1) if self.cfg_pg.use_coords else normals
+        voxel_feats = pointgroup_ops.voxelization(point_feats, v2p_map, self.cfg_pg.mode)
+        return {'picks': picks, 'xyz_original': coords_float, 'normals': normals, 'locs': locs, 'spatial_shape': spatial_shape, 'batch_size': batchsize,
+                'voxel_coords': voxel_coords, 'p2v_map': p2v_map, 'v2p_map': v2p_map, 'voxel_feats': voxel_feats,
+                'batch_offsets': torch.tensor(batch_offsets, dtype=torch.int32, device=dev)}
+
+    def predict(self, data):
+        """predicter.py:232-338: data['cloud_xyz'], ['cloud_normal'] (and ['cloud_rgb'], which the reference carries along and never
+        reads) -> labels_all (N) int64 numpy.  Keeps xyz_shifted like the reference, and xyz_original / pt_offsets (float32 numpy)."""
+        from . import segmentation, spconv
+        with torch.no_grad():
+            fe = self.front_end(data)
+            input_ = spconv.SparseConvTensor(fe['voxel_feats'], fe['voxel_coords'].int(), fe['spatial_shape'], fe['batch_size'])
+            ret = self.model(input_, fe['p2v_map'], fe['xyz_original'], fe['locs'][:, 0].int(), fe['batch_offsets'], epoch=self.model.prepare_epochs - 1)
+            labels_all = segmentation.instances_from_offsets(data['cloud_xyz'], fe['xyz_original'], ret['pt_offsets'], self.class_name)
+            self.xyz_shifted = segmentation.instances_from_offsets.xyz_shifted
+            self.xyz_original = fe['xyz_original'].cpu().numpy()
+            self.pt_offsets = ret['pt_offsets'].cpu().numpy()
+            return labels_all

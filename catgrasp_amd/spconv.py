@@ -162,23 +162,35 @@ def inverse_rules(book):
     return book.extra['inverse_nbr']
 
 
-def sparse_conv(features, nbr, weight, bias=None, scale=None, shift=None, residual=None):
-    """out[i] = bias + residual[i] + sum_k pro(features[nbr[i, k]]) @ weight[k], one launch.  weight (K, Cin, Cout)."""
+def sparse_conv(features, nbr, weight, bias=None, scale=None, shift=None, residual=None, features_b=None):
+    """out[i] = bias + residual[i] + sum_k pro(features[nbr[i, k]]) @ weight[k], one launch.  weight (K, Cin, Cout).
+    features_b: a second matrix with the same rows; the layer then reads the concatenation [features | features_b] (Cin = the sum of
+    their widths) without forming it (cg_sparse_conv_cat), with the bits of the launch on torch.cat((features, features_b), 1)."""
     K, cin, cout = weight.shape
     n_out = nbr.shape[0]
-    if features.shape[1] != cin:
-        raise ValueError(f'features have {features.shape[1]} channels, the layer takes {cin}')
+    cin_b = 0 if features_b is None else features_b.shape[1]
+    if features.shape[1] + cin_b != cin:
+        raise ValueError(f'features have {features.shape[1] + cin_b} channels, the layer takes {cin}')
+    if features_b is not None and features_b.shape[0] != features.shape[0]:
+        raise ValueError(f'features has {features.shape[0]} rows, features_b {features_b.shape[0]}')
     if nbr.shape[1] != K:
         raise ValueError(f'the rule book has {nbr.shape[1]} offsets, the weight {K}')
     if (scale is None) != (shift is None):
         raise ValueError('the prologue needs both scale and shift')
-    for name, t, shape in (('bias', bias, (cout,)), ('scale', scale, (cin,)), ('shift', shift, (cin,)), ('residual', residual, (n_out, cout))):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda):
-            raise ValueError(f'{name} must be a float32 device tensor of shape {shape}')
+    for name, t, shape in (('bias', bias, (cout,)), ('scale', scale, (cin,)), ('shift', shift, (cin,)), ('residual', residual, (n_out, cout)),
+                           ('features_b', features_b, (features.shape[0], cin_b))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda or t.device != features.device):
+            raise ValueError(f'{name} must be a float32 tensor of shape {shape} on the device of features')
     out = torch.empty((n_out, cout), dtype=torch.float32, device=features.device)
     cont = lambda t: None if t is None else t.detach().contiguous()
-    check(L.lib().cg_sparse_conv(_p(L.f32c(features)), features.shape[0], _p(L.i32c(nbr)), n_out, K, _p(L.f32c(cont(weight))), _p(cont(bias)),
-                                 _p(cont(scale)), _p(cont(shift)), _p(cont(residual)), cin, cout, _p(out), _stream()), 'cg_sparse_conv')
+    features_b = cont(features_b)
+    tail = (_p(L.f32c(cont(weight))), _p(cont(bias)), _p(cont(scale)), _p(cont(shift)), _p(cont(residual)))
+    if features_b is None:
+        check(L.lib().cg_sparse_conv(_p(L.f32c(features)), features.shape[0], _p(L.i32c(nbr)), n_out, K, *tail, cin, cout, _p(out), _stream()),
+              'cg_sparse_conv')
+    else:
+        check(L.lib().cg_sparse_conv_cat(_p(L.f32c(features)), features.shape[1], _p(L.f32c(features_b)), cin_b, features.shape[0], _p(L.i32c(nbr)),
+                                         n_out, K, *tail, cout, _p(out), _stream()), 'cg_sparse_conv_cat')
     return out
 
 
@@ -256,14 +268,16 @@ class SparseConvolution(SparseModule):
             raise ValueError(f'indice_key {self.indice_key!r} belongs to another kind of layer or another set of sites')
         return book.nbr, book.out_indices, book.out_spatial_shape
 
-    def forward(self, input, prologue=None, residual=None):
+    def forward(self, input, prologue=None, residual=None, features_b=None):
         """prologue: (scale, shift) per input channel, applied as max(x*scale + shift, 0) to the rows the layer reads.
-        residual: (n_out, Cout), added to the output rows."""
+        residual: (n_out, Cout), added to the output rows.
+        features_b: (N, C_b) float32 device rows of the same sites; the layer reads [input.features | features_b] (sparse_conv)."""
         feats = _device_features(input, self.weight, self.bias)
         scale, shift = prologue if prologue is not None else (None, None)
         nbr, out_indices, out_shape = self._rule_book(input)
         K = nbr.shape[1]
-        out = sparse_conv(feats, nbr, self.weight.detach().reshape(K, self.in_channels, self.out_channels), self.bias, scale, shift, residual)
+        out = sparse_conv(feats, nbr, self.weight.detach().reshape(K, self.in_channels, self.out_channels), self.bias, scale, shift, residual,
+                          None if features_b is None else features_b.detach().contiguous())
         res = SparseConvTensor(out, out_indices, out_shape, input.batch_size)
         res.indice_dict = input.indice_dict
         res.grid = input.grid
