@@ -110,8 +110,9 @@ __global__ __launch_bounds__(256) void voxelize_fp_kernel(const float* __restric
 // the tensors over.  Device formulation:
 //  * voxelization_idx = sort the packed (batch,x,y,z) keys (stable: ties keep point order), number the runs by their first
 //    point index (= the reference's first-appearance order), and fill the two maps -- kernels below + a device sort/scan.
-//  * bfs_cluster = connected components of the same-label neighbour graph by min-label propagation with pointer jumping;
-//    clusters are numbered by their smallest point index, which is the order the reference's seed loop discovers them in.
+//  * bfs_cluster = every point goes to the smallest index that reaches it along the same-label neighbour lists, by min-label
+//    propagation along the lists with pointer jumping (the connected components where the lists are symmetric); clusters are
+//    numbered by their smallest point index, their seed, which is the order the reference's seed loop discovers them in.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void voxel_pack_kernel(const long long* __restrict__ coords, int n, int ncol, long long* __restrict__ keys,
                                                          int* __restrict__ err_flag) {
@@ -152,6 +153,11 @@ __global__ __launch_bounds__(256) void voxel_fill_maps_kernel(const long long* _
   }
 }
 
+// One sweep of comp[v] -> min{u : v is reachable from u along the lists, through same-label points}, which is the seed the
+// reference's loop claims v from (bfs_cluster.cpp:65-80: the smallest such u is visited by no earlier seed, and its queue reaches v
+// first).  The lists are followed in the direction the queue follows them and in no other: a point hands its value to the points
+// it lists and takes nothing from them.  The ball query's 1000-neighbour cap cuts lists, so a point may list points that do not
+// list it back, and those must not join its cluster through it.  The pointer jump stays valid: comp[c] reaches c, and c reaches i.
 // Rows are clamped to the n_idx entries that exist and entries outside [0, n) are skipped: a truncated / corrupt CSR list can
 // make the result incomplete but never an out-of-bounds access (the host wrapper rejects such input before it gets here).
 __global__ __launch_bounds__(256) void cc_propagate_kernel(const int* __restrict__ label, const int* __restrict__ nbr, int n_idx,
@@ -163,11 +169,10 @@ __global__ __launch_bounds__(256) void cc_propagate_kernel(const int* __restrict
   const long s0 = start_len[2 * i], e0 = s0 + (long)start_len[2 * i + 1];
   const int s = (int)(s0 < 0 ? 0 : (s0 > n_idx ? n_idx : s0)), e = (int)(e0 < s ? s : (e0 > n_idx ? n_idx : e0));
   int c = comp[i];
-  for (int q = s; q < e; ++q) { const int j = nbr[q]; if ((unsigned)j < (unsigned)n && label[j] == li) c = min(c, comp[j]); }
   c = min(c, comp[c]);                                   // pointer jumping
   bool ch = false;
   if (c < comp[i]) { atomicMin(comp + i, c); ch = true; }
-  for (int q = s; q < e; ++q) {                          // push to the neighbours too: the relation is used symmetrically
+  for (int q = s; q < e; ++q) {                          // push to the listed points: the direction the reference's queue walks
     const int j = nbr[q];
     if ((unsigned)j < (unsigned)n && label[j] == li && comp[j] > c) { atomicMin(comp + j, c); ch = true; }
   }

@@ -162,11 +162,13 @@ def voxelization_idx(coords, batchsize, mode=4):
 
 def bfs_cluster(semantic_label, ball_query_idxs, start_len, threshold):
     """pointgroup_ops.bfs_cluster (BFSCluster.forward; bfs_cluster.cpp:34-121; called at pointgroup.py:240,245):
-    -> (cluster_idxs (sumNPoint,2) int32 [cluster id, point id], cluster_offsets (nCluster+1) int32).  Clusters = connected
-    components of the neighbour graph restricted to equal semantic labels with >= threshold points, numbered by their smallest
-    point index (the order the reference's seed loop finds them).  Members are listed in ascending point index; the reference
-    lists them in queue-visit order (same sets).  The neighbour relation is used symmetrically (it is symmetric unless the ball
-    query's 1000-neighbour cap truncated a list).  Host tensors are accepted like the reference's (pointgroup.py:240,245 pass
+    -> (cluster_idxs (sumNPoint,2) int32 [cluster id, point id], cluster_offsets (nCluster+1) int32).  A point belongs to the
+    smallest index that reaches it along the neighbour lists through points of its own semantic label -- the seed from which the
+    reference's queue BFS claims it; the clusters with >= threshold points are kept, numbered by that seed, their smallest point
+    index (the order the reference's seed loop finds them).  Members are listed in ascending point index; the reference lists
+    them in queue-visit order (same sets).  Lists are followed one way, as the reference follows them: where the ball query's
+    1000-neighbour cap cut a list, a point that lists a cluster's points without being listed by any of them stays outside it
+    (tests/golden/pointgroup_cap_golden.npz).  Host tensors are accepted like the reference's (pointgroup.py:240,245 pass
     `.cpu()` tensors) and the results returned on the inputs' device (see _on_device).  A CSR row that reaches past the end of
     `ball_query_idxs`, or an entry outside [0, N), raises (the reference's queue BFS would read out of bounds there)."""
     semantic_label, ball_query_idxs, start_len, home = _on_device(semantic_label, ball_query_idxs, start_len)

@@ -288,3 +288,93 @@ def test_robot_gripper_loader_matches_the_real_class(tmp_path):
         assert np.array_equal(data, gold[tag + '_sdf_data']) and np.array_equal(origin, gold[tag + '_sdf_origin']) and res == gold[tag + '_sdf_res'][0]
         data_e, origin_e, _ = sdf_mod.SdfFile(str(d / 'gripper_enclosed_air_tight.sdf')).read_arrays()
         assert np.array_equal(data_e, gold[tag + '_sdfe_data']) and np.array_equal(origin_e, gold[tag + '_sdfe_origin'])
+
+
+CAP_GOLD = os.path.join(os.path.dirname(GOLD), 'pointgroup_cap_golden.npz')
+
+
+@pytest.fixture(scope='module')
+def cap_scenes():
+    """tests/golden/pointgroup_cap_golden.npz (make_golden_pointgroup_cap.py): three scenes whose neighbour lists the ball query's
+    1000-neighbour cap cuts, with the clusters of the reference's own queue BFS.  The neighbour array is not stored: it is rebuilt
+    here once, by the restated ball query -> {scene: (label, idx, start_len)}, read-only."""
+    from oracle import pointgroup_ops_ref as ref
+    g = np.load(CAP_GOLD)
+    out = {}
+    for name in g['scenes']:
+        xyz = g[f'{name}_xyz']
+        n = len(xyz)
+        idx, start_len, _ = ref.ballquery_batch_p(xyz, np.zeros(n, dtype=np.int32), np.array([0, n], dtype=np.int32), float(g['radius']), 300)
+        for a in (idx, start_len):
+            a.setflags(write=False)
+        out[str(name)] = (g[f'{name}_label'], idx, start_len)
+    return g, out
+
+
+def test_pointgroup_cap_fixture_from_the_restated_ball_query_and_bfs(cap_scenes):
+    """ref.ballquery_batch_p -> ref.bfs_cluster on the capped scenes vs the reference's own host BFS (bfs_cluster.cpp:33-91):
+    the counts (capped at 1000 on every scene), offsets, cluster ids and the members in the queue's visit order, at both thresholds."""
+    from oracle import pointgroup_ops_ref as ref
+    g, scenes = cap_scenes
+    assert sorted(scenes) == ['bar', 'blob1300', 'bridged']
+    for name, (label, idx, start_len) in scenes.items():
+        counts = g[f'{name}_counts']
+        assert np.array_equal(start_len[:, 1], counts) and counts.max() == 1000 and (counts == 1000).sum() > 500
+        assert len(idx) == int(counts.sum()) and np.array_equal(start_len[:, 0], np.cumsum(counts) - counts)
+        for thr in (1, 50):
+            ci, co = ref.bfs_cluster(label, idx, start_len, thr)
+            assert np.array_equal(co, g[f'{name}_thr{thr}_cluster_offsets']) and np.array_equal(ci, g[f'{name}_thr{thr}_cluster_idxs'])
+        assert len(g[f'{name}_thr50_cluster_offsets']) - 1 >= 2
+
+
+def push_only_owner(label, idx, start_len):
+    """What cg_pg_cc_propagate must converge to, written out: owner[v] = min{u : v is reachable from u along the lists through
+    same-label points}.  Synchronous sweeps of the kernel's body: a pointer jump c = min(comp, comp[comp]), then every point
+    hands c to the points it lists (and takes nothing from them).  -> (owner, number of sweeps that changed something)."""
+    n = len(start_len)
+    src = np.repeat(np.arange(n), start_len[:, 1]); dst = idx.astype(np.int64)
+    same = label[src] == label[dst]
+    src, dst = src[same], dst[same]
+    comp = np.arange(n)
+    sweeps = 0
+    while True:
+        c = np.minimum(comp, comp[comp])                     # pointer jumping
+        new = c.copy()
+        np.minimum.at(new, dst, c[src])                      # push along the lists
+        if np.array_equal(new, comp):
+            return comp, sweeps
+        comp = new; sweeps += 1
+
+
+def clusters_of_owner(owner, threshold):
+    """owner (n) -> (cluster_idxs, cluster_offsets) as catgrasp_amd.pointgroup_ops.bfs_cluster returns them: clusters of >= threshold
+    points, numbered by their owner in ascending order, members in ascending point index."""
+    keep = np.bincount(owner, minlength=len(owner))[owner] >= threshold
+    pts = np.flatnonzero(keep)
+    pts = pts[np.argsort(owner[pts], kind='stable')]
+    roots, inverse, sizes = np.unique(owner[pts], return_inverse=True, return_counts=True)
+    return np.stack([inverse, pts], 1).astype(np.int32), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def test_min_over_ancestors_propagation_gives_the_reference_clusters(cap_scenes):
+    """The push-only rule reproduces the reference's clusters on cut lists: same offsets, same numbering, same members as sets (the
+    reference lists them in visit order).  On blob1300 and bridged the rule must differ from what pulling as well would give
+    (undirected components), or the scenes would not tell the two apart."""
+    g, scenes = cap_scenes
+    for name, (label, idx, start_len) in scenes.items():
+        owner, sweeps = push_only_owner(label, idx, start_len)
+        assert 1 <= sweeps <= 8                               # a blob's cut lists are at most 3 hops deep, one hop per sweep at worst
+        assert (owner <= np.arange(len(owner))).all() and np.array_equal(owner[owner], owner)
+        for thr in (1, 50):
+            ci, co = clusters_of_owner(owner, thr)
+            rci, rco = g[f'{name}_thr{thr}_cluster_idxs'], g[f'{name}_thr{thr}_cluster_offsets']
+            assert np.array_equal(co, rco) and np.array_equal(ci[:, 0], rci[:, 0])
+            for c in range(len(rco) - 1):
+                assert np.array_equal(ci[rco[c]:rco[c + 1], 1], np.sort(rci[rco[c]:rco[c + 1], 1]))
+        # with the lists read both ways (every entry an undirected edge) the big blobs swallow the points nobody lists
+        rev_idx = np.repeat(np.arange(len(start_len)), start_len[:, 1]).astype(np.int32)
+        both = np.concatenate([np.stack([rev_idx, idx], 1), np.stack([idx, rev_idx], 1)])
+        both = both[np.argsort(both[:, 0], kind='stable')]
+        cnt = np.bincount(both[:, 0], minlength=len(start_len))
+        und, _ = push_only_owner(label, both[:, 1], np.stack([np.cumsum(cnt) - cnt, cnt], 1))
+        assert np.array_equal(und, owner) == (name == 'bar')
