@@ -25,8 +25,9 @@ def direction_vec_to_rotation(direction, ref):
 
 
 class ConeSampler:
-    def __init__(self, r_ball, hand_depth, init_bite, approach_step):
+    def __init__(self, r_ball, hand_depth, init_bite, approach_step, inplane_step_deg=30):
         self.r_ball = r_ball; self.hand_depth = hand_depth; self.init_bite = init_bite; self.approach_step = approach_step
+        self.inplane_step_deg = inplane_step_deg      # the reference hard-codes 30 (:274)
 
     def sample_one_surface_point(self, p, n, pts, nrms, sphere_pts, flip_minor=False):
         tree = cKDTree(pts)
@@ -57,7 +58,7 @@ class ConeSampler:
         Rs = [R0]
         for sp in sphere_pts:
             Rsph = direction_vec_to_rotation(sp.copy(), np.array([1., 0, 0]))
-            for x_rot in np.arange(0, 180, 30):
+            for x_rot in np.arange(0, 180, self.inplane_step_deg):
                 ang = x_rot * np.pi / 180
                 Rx = np.array([[1, 0, 0], [0, np.cos(ang), -np.sin(ang)], [0, np.sin(ang), np.cos(ang)]])
                 Rs.append(R0 @ Rsph @ Rx)
