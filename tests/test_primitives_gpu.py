@@ -204,7 +204,8 @@ def test_sample_and_group(cuda_device):
 
 
 # register-resident kernel: 1..3 layers of width 32 / 64 / 128, one / two / four neighbourhoods per 32-row tile (K <= 32 / 16 / 8) and
-# several row tiles (K = 40, 64); strip kernel: a 256-wide layer, a 96-wide layer, four layers
+# several row tiles (K = 40, 33); strip kernel: the four-layer net (3, 16, [32, 32, 64, 64]) only -- through the module a 256-wide
+# layer (13, 64, [128, 128, 256]) and a 96-wide one (6, 32, [64, 96, 128]) select kind='tile', the kernel of csrc/sa_tile.hip
 @pytest.mark.parametrize('D,K,mlp', [(6, 32, [64, 64, 128]), (0, 16, [32, 64]), (13, 64, [128, 128, 256]), (3, 40, [64]), (6, 8, [32, 32, 64]),
                                      (2, 12, [128, 128, 128]), (6, 5, [128]), (0, 32, [32]), (9, 16, [64, 128]), (6, 33, [128, 64, 32]),
                                      (6, 32, [64, 96, 128]), (3, 16, [32, 32, 64, 64]), (6, 24, [128, 128, 128])])
