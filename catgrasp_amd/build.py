@@ -35,7 +35,8 @@ def build(force=False, verbose=True):
         if _stale(inc, [gen]):      # the hand-scheduled instruction streams of pointmlp_split.hip / pointmlp.hip are generated text
             subprocess.check_call([sys.executable, gen])
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hpp', '.inc'))]
-    hdrs += [os.path.join(PKG_DIR, '..', 'include', h) for h in ('catgrasp_amd.h', 'catgrasp_amd_cluster.h', 'catgrasp_amd_sparse.h', 'catgrasp_amd_pointgroup.h')]
+    hdrs += [os.path.join(PKG_DIR, '..', 'include', h) for h in ('catgrasp_amd.h', 'catgrasp_amd_cluster.h', 'catgrasp_amd_sparse.h', 'catgrasp_amd_pointgroup.h',
+                                                                 'catgrasp_amd_scene.h')]
     objs = []
     jobs = []
     for s in srcs:

@@ -20,6 +20,7 @@ import torch
 
 from . import affordance as aff_mod
 from . import grasp_sampler, my_cpp, transforms
+from .scene import scene_from_depth  # noqa: F401  (the front end belongs to the pick cycle: re-exported)
 
 
 def _background_points(scene_pts, ob_pts, gripper_diameter, device):
@@ -380,3 +381,10 @@ def objects_from_scene(data, predictor, **select_kw):
     labels = predictor.predict(data)
     cleaned, order = segmentation.select_segments(np.asarray(data['cloud_xyz']), labels, **select_kw)
     return objects_from_segmentation(data['cloud_xyz'], data['cloud_normal'], cleaned, order)
+
+
+def objects_from_depth(depth, K, predictor, rgb=None, bg_mask=None, **select_kw):
+    """Depth image -> (the object list `evaluate_objects` consumes, scene_pts): `scene.scene_from_depth` (xyz map, masks, oriented
+    normals, down-sampled scene points; run_grasp_simulation.py:192-212, :245-250), then `objects_from_scene` on its cloud."""
+    front = scene_from_depth(depth, K, rgb=rgb, bg_mask=bg_mask)
+    return objects_from_scene(front['data'], predictor, **select_kw), front['scene_pts']

@@ -252,3 +252,26 @@ def background_points(objs, k, gripper_diameter):
     pts = np.concatenate(others)
     d, _ = tree.query(pts)
     return pts[d <= gripper_diameter / 2]
+
+
+def make_depth_image(H, W, K, n_spheres, seed):
+    """A synthetic depth frame (H, W) float32 in metres: a floor plane facing the camera obliquely and n_spheres spheres resting
+    above it, each pixel's depth by exact ray intersection (the nearest hit along the pixel's ray (x/z, y/z, 1))."""
+    rng = np.random.default_rng(seed)
+    K = np.asarray(K, dtype=np.float64)
+    vs, us = np.meshgrid(np.arange(H), np.arange(W), indexing='ij')
+    rx, ry = (us - K[0, 2]) / K[0, 0], (vs - K[1, 2]) / K[1, 1]
+    # plane n . p = d with p = z (rx, ry, 1)
+    nrm = np.array([0.05, -0.08, -1.0]) / np.linalg.norm([0.05, -0.08, -1.0])
+    d_plane = nrm @ np.array([0.0, 0.0, 0.65])
+    depth = d_plane / (nrm[0] * rx + nrm[1] * ry + nrm[2])
+    xmax, ymax = 0.36 * np.abs(rx).max(), 0.36 * np.abs(ry).max()          # centres within the middle of the view at z ~ 0.6
+    rr = rx * rx + ry * ry + 1.0
+    for _ in range(n_spheres):
+        rad = rng.uniform(0.01, 0.03)
+        c = np.array([rng.uniform(-xmax, xmax), rng.uniform(-ymax, ymax), rng.uniform(0.55, 0.62)])
+        b = rx * c[0] + ry * c[1] + c[2]                     # z^2 rr - 2 z b + |c|^2 - rad^2 = 0
+        disc = b * b - rr * (c @ c - rad * rad)
+        z = (b - np.sqrt(np.where(disc >= 0, disc, 0.0))) / rr
+        depth = np.where((disc >= 0) & (z < depth), z, depth)
+    return depth.astype(np.float32)
