@@ -20,6 +20,10 @@ at o reads, through kernel offset kk, the input at o*stride - padding + kk; abse
 Layers that share an `indice_key` share one rule book (stored in the tensor's `indice_dict`).  A SparseSequential in eval mode runs
 `BatchNorm1d, ReLU, conv` as the conv's prologue max(x*scale + shift, 0) on the gathered rows; the conv layers also take an
 optional `residual` that is added to the output rows in the same launch.
+
+The prologue's max is C's fmaxf, which returns 0 for a NaN: a NaN feature (or a NaN in scale or shift) enters a folded
+`BatchNorm1d, ReLU, conv` as 0, where torch.relu in the unfolded sequence would hand it on.  Without a prologue a NaN feature makes
+every column of the rows that read its site NaN, and no other row.
 """
 import math
 from collections import OrderedDict, namedtuple

@@ -65,6 +65,9 @@ int cg_sparse_rules_inverse(const int* indices, long n_in, const long long* out_
  *   out[i] = bias + residual[i] + sum_k pro(feats[nbr[i,k]]) * weight[k]      (k ascending, absent entries skipped)
  * feats (n_in, cin) f32, nbr (n_out, K) i32 with entries in [-1, n_in), weight (K, cin, cout) f32, bias (cout) or NULL,
  * pro(x)[c] = max(x[c]*scale[c] + shift[c], 0) when scale and shift (cin) are given (both or neither), else x;
+ * the product and the sum are rounded separately, and the max is C's fmaxf: a NaN in x, scale or shift gives 0, it is
+ * not handed on as a ReLU on its own would (without a prologue a NaN reaches every column of the rows that read it);
+ * the sum over k and the input channels is a chain of f32 fmaf from +0, then (sum + bias) + residual;
  * residual (n_out, cout) or NULL; out (n_out, cout), written once per row.  K in {1, 8, 27}.
  * cin in {6, multiples of 16 up to 224}, cout in {3, multiples of 16 up to 112}: anything else is CG_ERR_UNSUPPORTED.
  * Deterministic: every output row is one wave's fixed-order f32 sum, no atomics. */
