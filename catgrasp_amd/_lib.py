@@ -14,7 +14,8 @@ The clustering entry points have a header of their own, include/catgrasp_amd_clu
 `declared_symbols()` describe the main header, `cluster_signatures()` the other.  The sparse convolution layers have a third,
 include/catgrasp_amd_sparse.h, described by `sparse_signatures()`, and the assembled PointGroup network a fourth,
 include/catgrasp_amd_pointgroup.h, described by `pointgroup_signatures()`, and the scene front end (depth image -> point normals) a
-fifth, include/catgrasp_amd_scene.h, described by `scene_signatures()`.  `lib()` binds and requires all five.
+fifth, include/catgrasp_amd_scene.h, described by `scene_signatures()`, and the grid index (neighbour queries and normals of any cloud)
+a sixth, include/catgrasp_amd_neighbors.h, described by `neighbors_signatures()`.  `lib()` binds and requires all six.
 """
 import ctypes
 import os
@@ -29,6 +30,7 @@ CLUSTER_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_cluster.
 SPARSE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_sparse.h')     # the sparse convolution layers: likewise
 POINTGROUP_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_pointgroup.h')   # the assembled PointGroup network: likewise
 SCENE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_scene.h')     # the scene front end: likewise
+NEIGHBORS_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_neighbors.h')   # the grid index: likewise
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -98,6 +100,12 @@ def scene_signatures():
         return signatures(f.read())
 
 
+def neighbors_signatures():
+    """signatures() of include/catgrasp_amd_neighbors.h: same parser, same type mapping."""
+    with open(NEIGHBORS_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -106,7 +114,8 @@ def lib():
                 f'{LIB_PATH} not found: build it with `python -m catgrasp_amd.build` '
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
-        sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures()}
+        sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures(),
+                **neighbors_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')

@@ -21,6 +21,7 @@
 // run the same arithmetic on the same candidates in the same order, so their outputs are the same bits.  A query whose window
 // exceeds the staged halo reads global memory in the TILED kernel as well: the halo is a matter of speed, not of results.
 #include "cg_common.hpp"
+#include "cg_normals.hpp"
 #include "../../include/catgrasp_amd_scene.h"
 #include <math.h>
 #include <string.h>
@@ -124,38 +125,6 @@ __device__ __forceinline__ Moments accumulate(const Source& s, const Query& q, l
   return m;
 }
 
-// One Jacobi rotation of a symmetric 3 x 3 matrix in the (p, q) plane: app, aqq, apq the rotated block, arp, arq the third index's
-// row, (v?p, v?q) the two columns of the accumulated eigenvector matrix.
-__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
-                                              double& v1p, double& v1q, double& v2p, double& v2q) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));   // the smaller root: |angle| <= pi/4
-  const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-  app -= t * apq; aqq += t * apq; apq = 0.0;
-  double a = arp, b = arq;
-  arp = c * a - sn * b; arq = sn * a + c * b;
-  a = v0p; b = v0q; v0p = c * a - sn * b; v0q = sn * a + c * b;
-  a = v1p; b = v1q; v1p = c * a - sn * b; v1q = sn * a + c * b;
-  a = v2p; b = v2q; v2p = c * a - sn * b; v2q = sn * a + c * b;
-}
-
-// unit eigenvector of the smallest eigenvalue of the symmetric matrix (a00 a01 a02; . a11 a12; . . a22): cyclic Jacobi
-__device__ __forceinline__ void smallest_eigenvector(double a00, double a01, double a02, double a11, double a12, double a22, double& nx,
-                                                     double& ny, double& nz) {
-  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    if (fabs(a01) + fabs(a02) + fabs(a12) <= 1e-19 * (fabs(a00) + fabs(a11) + fabs(a22))) break;
-    jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-    jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-    jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-  }
-  const bool c0 = a00 <= a11 && a00 <= a22, c1 = !c0 && a11 <= a22;
-  nx = c0 ? v00 : c1 ? v01 : v02; ny = c0 ? v10 : c1 ? v11 : v12; nz = c0 ? v20 : c1 ? v21 : v22;
-  const double len = sqrt(nx * nx + ny * ny + nz * nz);
-  nx /= len; ny /= len; nz /= len;
-}
-
 template <bool TILED>
 __global__ __launch_bounds__(SC_THREADS) void organized_normals_kernel(const float* __restrict__ xyz, const unsigned char* __restrict__ use,
                                                                        int H, int W, double fx, double fy, double cx, double cy,
@@ -232,19 +201,8 @@ __global__ __launch_bounds__(SC_THREADS) void organized_normals_kernel(const flo
     m = accumulate(s, q, hi, ties);
   }
 
-  double nx = 0.0, ny = 0.0, nz = 1.0;                      // open3d's normal of a point with fewer than 3 neighbours
-  if (m.n >= 3) {
-    const double n = (double)m.n, mx = m.sx / n, my = m.sy / n, mz = m.sz / n;
-    smallest_eigenvector(m.sxx / n - mx * mx, m.sxy / n - mx * my, m.sxz / n - mx * mz, m.syy / n - my * my, m.syz / n - my * mz,
-                         m.szz / n - mz * mz, nx, ny, nz);
-  }
-  // correct_pcd_normal_direction
-  const double len = sqrt(nx * nx + ny * ny + nz * nz) + 1e-10;
-  nx /= len; ny /= len; nz /= len;
-  double wx = vx - q.x, wy = vy - q.y, wz = vz - q.z;
-  const double wl = sqrt(wx * wx + wy * wy + wz * wz);
-  wx /= wl; wy /= wl; wz /= wl;
-  if (wx * nx + wy * ny + wz * nz < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+  double nx, ny, nz;
+  oriented_normal(m, q.x, q.y, q.z, vx, vy, vz, nx, ny, nz);
   normals[pix * 3] = nx; normals[pix * 3 + 1] = ny; normals[pix * 3 + 2] = nz;
   if (nb_count) nb_count[pix] = m.n;
   if (nb_d2max) nb_d2max[pix] = __longlong_as_double(m.d2max);

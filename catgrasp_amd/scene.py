@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import neighbors
 from ._lib import _p, _stream, check
 from .aligning import voxel_down_sample_device
 
@@ -134,17 +135,22 @@ def estimate_normals_organized(xyz_map, use, K, radius=0.002, max_nn=30, view_po
     return (normals, count, d2max) if debug else normals
 
 
-def scene_from_depth(depth, K, rgb=None, bg_mask=None, radius=0.002, max_nn=30, scene_voxel=0.001, return_tensor=False):
+def scene_from_depth(depth, K, rgb=None, bg_mask=None, radius=0.002, max_nn=30, scene_voxel=0.001, return_tensor=False,
+                     scene_normal_radius=None):
     """run_grasp_simulation.py:192-212 and :245-250 -> {'data': {'cloud_xyz', ['cloud_rgb',] 'cloud_normal'}, 'scene_pts'}.
     bg_mask: (H, W), non-zero for pixels that belong to the background (the reference marks the environment's bodies); invalid
     depth (< 0.1) is background by itself.  data['cloud_xyz']: float32 xyz_map[use] in row-major order, use = valid and not background;
     data['cloud_rgb']: rgb[use], only with `rgb` (H, W, 3); data['cloud_normal']: float64 oriented normals (radius, max_nn, view
     point at the camera).  scene_pts: the valid points voxel-down-sampled at `scene_voxel` (float64 centroids; colours are not
-    averaged).  numpy arrays unless return_tensor."""
+    averaged).  With scene_normal_radius (the reference's value is 0.003) the result also holds 'scene_normals': the oriented normals
+    of scene_pts, an unorganized cloud, by neighbors.estimate_normals (run_grasp_simulation.py:247-248).  numpy arrays unless
+    return_tensor."""
     _intrinsics(K)
     _check_search(radius, max_nn)
     if not (isinstance(scene_voxel, (int, float, np.floating, np.integer)) and math.isfinite(scene_voxel) and scene_voxel > 0):
         raise ValueError(f'scene_voxel must be a positive finite number, got {scene_voxel!r}')
+    if scene_normal_radius is not None:
+        _check_search(scene_normal_radius, max_nn)
     shape = tuple(depth.shape)
     if bg_mask is not None and tuple(bg_mask.shape) != shape:
         raise ValueError(f'bg_mask must have the image\'s shape {shape}, got {tuple(bg_mask.shape)}')
@@ -162,7 +168,10 @@ def scene_from_depth(depth, K, rgb=None, bg_mask=None, radius=0.002, max_nn=30, 
     if colours is not None:
         data['cloud_rgb'] = colours
     scene_pts = voxel_down_sample_device(xyz_map[valid].to(torch.float64), float(scene_voxel))
+    out = {'data': data, 'scene_pts': scene_pts}
+    if scene_normal_radius is not None:
+        out['scene_normals'] = neighbors.estimate_normals(scene_pts, radius=scene_normal_radius, max_nn=max_nn, return_tensor=True)
     if not return_tensor:
-        data = {k: v.cpu().numpy() for k, v in data.items()}
-        scene_pts = scene_pts.cpu().numpy()
-    return {'data': data, 'scene_pts': scene_pts}
+        out['data'] = {k: v.cpu().numpy() for k, v in data.items()}
+        out.update({k: v.cpu().numpy() for k, v in out.items() if k != 'data'})
+    return out
