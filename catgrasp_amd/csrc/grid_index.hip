@@ -12,9 +12,13 @@
 // it and the list is read once for the new worst.  The list lives in LDS because it is indexed at run time; in registers it would go to
 // scratch.  Afterwards the d2 slots take the original indices, and the moments are accumulated over the list in ascending original
 // index by selection (max_nn^2 LDS reads), which is the order cg_organized_normals accumulates in.
+//
+// On the same tables (include/catgrasp_amd_kdtree.h): the unbounded exact nearest neighbour, by boxes of doubling radius with a linear
+// pass as the bound on its work, and the index lists behind the counts.  DESIGN 4.12.1.
 #include "cg_common.hpp"
 #include "cg_normals.hpp"
 #include "../../include/catgrasp_amd_neighbors.h"
+#include "../../include/catgrasp_amd_kdtree.h"
 #include <float.h>
 #include <limits.h>
 #include <math.h>
@@ -64,6 +68,22 @@ __device__ __forceinline__ Range cell_range(double q, double reach, double o, do
   return r;
 }
 
+// the first sorted position with key >= k0, in [0, n]
+__device__ __forceinline__ long first_key_at_least(const Grid& g, long long k0) {
+  long a = 0, b = g.n;
+  while (a < b) {
+    const long mid = a + ((b - a) >> 1);
+    if (g.keys[mid] < k0) a = mid + 1; else b = mid;
+  }
+  return a;
+}
+
+// the pinned d2 of sorted point j, as bits: non-negative doubles order like their bits; NaN and infinity are above every finite one
+__device__ __forceinline__ long long d2_bits(const Grid& g, long j, double qx, double qy, double qz) {
+  const double dx = __dsub_rn(g.pts[j * 3], qx), dy = __dsub_rn(g.pts[j * 3 + 1], qy), dz = __dsub_rn(g.pts[j * 3 + 2], qz);
+  return __double_as_longlong(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+}
+
 // f(j, d2 bits, dx, dy, dz) for every sorted position j whose point is in range of q: the query's own cell row, then the others;
 // ascending j within a row
 template <typename F>
@@ -78,12 +98,7 @@ __device__ __forceinline__ void for_each_in_range(const Grid& g, double qx, doub
       for (long cy = ry.lo; cy <= ry.hi; ++cy) {
         if ((cz == hz && cy == hy) != (pass == 0)) continue;
         const long long row = ((long long)cz * g.ey + cy) * g.ex, k0 = row + rx.lo, k1 = row + rx.hi;
-        long a = 0, b = g.n;                                // the first position with key >= k0, in [0, n]
-        while (a < b) {
-          const long mid = a + ((b - a) >> 1);
-          if (g.keys[mid] < k0) a = mid + 1; else b = mid;
-        }
-        for (long j = a; j < g.n && g.keys[j] <= k1; ++j) {
+        for (long j = first_key_at_least(g, k0); j < g.n && g.keys[j] <= k1; ++j) {
           const double dx = __dsub_rn(g.pts[j * 3], qx), dy = __dsub_rn(g.pts[j * 3 + 1], qy), dz = __dsub_rn(g.pts[j * 3 + 2], qz);
           const long long bits = __double_as_longlong(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
           if (bits <= r2_bits) f(j, bits, dx, dy, dz);     // non-negative doubles order like their bits; NaN and infinity are above
@@ -185,6 +200,147 @@ __global__ __launch_bounds__(NB_Q_THREADS) void grid_query_kernel(Grid g, const 
   }
 }
 
+// the running minimum by (d2 bits, original index); whether the candidate took its place
+struct Best { long long b; int i; };
+__device__ __forceinline__ bool take_nearer(Best& best, const Grid& g, long j, long long b) {
+  if (b > best.b) return false;
+  const int i = g.index[j];
+  if (!(b < best.b || i < best.i)) return false;
+  best.b = b; best.i = i;
+  return true;
+}
+
+struct Box { Range x, y, z; };
+__device__ __forceinline__ Range meet(Range a, Range b) {
+  const Range r = {a.lo > b.lo ? a.lo : b.lo, a.hi < b.hi ? a.hi : b.hi};
+  return r;
+}
+
+// `box` without the cells that cannot hold a point with d2 <= best: rho = sqrt(max(best, 2^-900)) (1 + 2^-40) has fl(rho^2) >= best, a
+// normal number, so by the lemma at cell_range such a point lies in cell_range(q, rho (1 + 2^-40)) on every axis.  A point outside has
+// d2 > best and can neither beat nor tie it, now or later: the best only falls.  No pruning while best is infinite (nothing found yet).
+__device__ __forceinline__ Box cells_within_best(const Grid& g, double qx, double qy, double qz, long long best_bits, Box box) {
+  const double b = __longlong_as_double(best_bits);
+  if (!(b <= 0x1p1000)) return box;
+  const double rho = __dmul_rn(sqrt(b >= 0x1p-900 ? b : 0x1p-900), 1.0 + 0x1p-40), reach = __dmul_rn(rho, 1.0 + 0x1p-40);
+  box.x = meet(box.x, cell_range(qx, reach, g.ox, g.cell, g.ex));
+  box.y = meet(box.y, cell_range(qy, reach, g.oy, g.cell, g.ey));
+  box.z = meet(box.z, cell_range(qz, reach, g.oz, g.cell, g.ez));
+  return box;
+}
+
+// A lower bound, rounded down and >= 0, of |p - q| on one axis over the points p of cell c, h being the (clamped) cell of q; 0 where
+// none is known.  c() is monotone, clamp included, so a double x with c(x) < c lies below every such p and one with c(x) > c above
+// it: x is a guess at the cell's face, nudged 2^-30 of its offset towards q, and counts only if c(x) -- evaluated, not assumed --
+// says so.
+__device__ __forceinline__ double axis_gap(double q, long c, long h, double o, double cell, long ext) {
+  double gap = 0.0;
+  if (c > h) {
+    const double x = __dadd_rn(o, __dmul_rn(__dmul_rn((double)c, cell), 1.0 - 0x1p-30));
+    if (clamp_cell(cell_coord(x, o, cell), ext) < c) gap = nextafter(__dsub_rn(x, q), -INFINITY);
+  } else if (c < h) {
+    const double x = __dadd_rn(o, __dmul_rn(__dmul_rn((double)(c + 1), cell), 1.0 + 0x1p-30));
+    if (clamp_cell(cell_coord(x, o, cell), ext) > c) gap = nextafter(__dsub_rn(q, x), -INFINITY);
+  }
+  return gap > 0.0 ? gap : 0.0;
+}
+
+// The cells along x of a row whose points lie at least gy and gz from q on the other axes that can hold a point with d2 <= best
+// (empty: none).  fl(d2) <= best needs dy^2 + dz^2 <= best (1 + 2^-50) in real numbers (rounding is monotone and the terms are
+// non-negative), so the row is out once (gy^2 + gz^2)(1 - 2^-40) > best, and otherwise dx^2 <= rem = best (1 + 2^-40) - (gy^2 + gz^2)
+// (1 - 2^-40), whose rounding the two 2^-40 cover; the range is cell_range at sqrt(rem) (1 + 2^-40).  best is taken as at least
+// 2^-900, so that rem is a normal number; above 2^1000 (nothing found yet) the row keeps the whole range.
+__device__ __forceinline__ Range row_cells_within_best(const Grid& g, double qx, double gy, double gz, long long best_bits, Range x) {
+  const double b = __longlong_as_double(best_bits);
+  if (!(b <= 0x1p1000)) return x;
+  const double bb = b >= 0x1p-900 ? b : 0x1p-900;
+  const double low = __dmul_rn(__dadd_rn(__dmul_rn(gy, gy), __dmul_rn(gz, gz)), 1.0 - 0x1p-40);
+  const Range none = {0, -1};
+  if (low > bb) return none;
+  const double rho = __dmul_rn(sqrt(__dsub_rn(__dmul_rn(bb, 1.0 + 0x1p-40), low)), 1.0 + 0x1p-40);
+  return meet(x, cell_range(qx, __dmul_rn(rho, 1.0 + 0x1p-40), g.ox, g.cell, g.ex));
+}
+
+// The unbounded nearest neighbour (include/catgrasp_amd_kdtree.h): boxes of radius cell * 2^k around q until the best d2 is within
+// the box's radius -- by the lemma at cell_range every point that could beat or tie it has then been seen -- or the box is the whole
+// lattice; one linear pass over the table instead once a round would search more rows than there are points, or after
+// CG_KD_MAX_ROUNDS rounds.  A box is scanned from the query's own row of cells outwards, and whenever a row lowers the best, the box
+// shrinks to the cells that can still hold something as near (cells_within_best); a row of cells farther from q than the best is
+// skipped and the others are searched only as far along x as the best allows (row_cells_within_best).  Every sorted position read
+// is in [0, n).
+template <typename T>
+__global__ __launch_bounds__(NB_Q_THREADS) void grid_nearest_kernel(Grid g, const T* __restrict__ queries, const int* __restrict__ order, long m,
+                                                                    int* __restrict__ nn_index, double* __restrict__ nn_d2,
+                                                                    int* __restrict__ rounds) {
+  const long t = (long)blockIdx.x * NB_Q_THREADS + threadIdx.x;
+  if (t >= m) return;
+  const long q = order ? (long)order[t] : t;
+  const double qx = (double)queries[q * 3], qy = (double)queries[q * 3 + 1], qz = (double)queries[q * 3 + 2];
+  // the query's own cell, clamped into the lattice: inside every non-empty cell_range around q
+  const long hy = clamp_cell(cell_coord(qy, g.oy, g.cell), g.ey), hz = clamp_cell(cell_coord(qz, g.oz, g.cell), g.ez);
+  Best best = {LLONG_MAX, INT_MAX};
+  double r = g.cell;                                        // doubled every round: exact
+  int k = 0;
+  bool done = false;
+  while (k < CG_KD_MAX_ROUNDS) {
+    const double reach = __dmul_rn(r, 1.0 + 0x1p-40);
+    const Box box = {cell_range(qx, reach, g.ox, g.cell, g.ex), cell_range(qy, reach, g.oy, g.cell, g.ey),
+                     cell_range(qz, reach, g.oz, g.cell, g.ez)};
+    Box live = cells_within_best(g, qx, qy, qz, best.b, box);
+    if (live.x.lo <= live.x.hi && live.y.lo <= live.y.hi && live.z.lo <= live.z.hi) {
+      if (k > 0 && (long long)(live.y.hi - live.y.lo + 1) * (live.z.hi - live.z.lo + 1) > (long long)g.n) break;   // the work bound
+      for (long sz = 0; hz + sz <= live.z.hi || hz - sz >= live.z.lo; ++sz)
+        for (int uz = 0; uz < (sz ? 2 : 1); ++uz) {
+          const long cz = uz ? hz - sz : hz + sz;
+          if (cz < live.z.lo || cz > live.z.hi) continue;
+          const double gz = axis_gap(qz, cz, hz, g.oz, g.cell, g.ez);
+          for (long sy = 0; hy + sy <= live.y.hi || hy - sy >= live.y.lo; ++sy)
+            for (int uy = 0; uy < (sy ? 2 : 1); ++uy) {
+              const long cy = uy ? hy - sy : hy + sy;
+              if (cy < live.y.lo || cy > live.y.hi || cz < live.z.lo || cz > live.z.hi) continue;
+              const Range x = row_cells_within_best(g, qx, axis_gap(qy, cy, hy, g.oy, g.cell, g.ey), gz, best.b, live.x);
+              if (x.lo > x.hi) continue;
+              const long long row = ((long long)cz * g.ey + cy) * g.ex, k1 = row + x.hi;
+              bool nearer = false;
+              for (long j = first_key_at_least(g, row + x.lo); j < g.n && g.keys[j] <= k1; ++j)
+                nearer |= take_nearer(best, g, j, d2_bits(g, j, qx, qy, qz));
+              if (nearer) live = cells_within_best(g, qx, qy, qz, best.b, live);
+            }
+        }
+    }
+    ++k;
+    const double r2 = __dmul_rn(r, r);
+    if (r2 >= DBL_MIN && r2 <= DBL_MAX && best.b <= __double_as_longlong(r2)) { done = true; break; }
+    if (box.x.lo == 0 && box.x.hi == g.ex - 1 && box.y.lo == 0 && box.y.hi == g.ey - 1 && box.z.lo == 0 && box.z.hi == g.ez - 1) {
+      done = true;                                          // the whole lattice: an empty range is {0, -1}, never this
+      break;
+    }
+    r = __dmul_rn(r, 2.0);
+  }
+  if (!done)
+    for (long j = 0; j < g.n; ++j) take_nearer(best, g, j, d2_bits(g, j, qx, qy, qz));
+  nn_index[q] = best.i;
+  nn_d2[q] = __longlong_as_double(best.b);
+  if (rounds) rounds[q] = done ? k : -k;
+}
+
+// the original indices of the points in range, in scan order, into the query's segment [offsets[q], offsets[q + 1]) of `indices`
+template <typename T>
+__global__ __launch_bounds__(NB_Q_THREADS) void grid_ball_fill_kernel(Grid g, const T* __restrict__ queries, const int* __restrict__ order, long m,
+                                                                      double reach, long long r2_bits, const long long* __restrict__ offsets,
+                                                                      long total, int* __restrict__ indices) {
+  const long t = (long)blockIdx.x * NB_Q_THREADS + threadIdx.x;
+  if (t >= m) return;
+  const long q = order ? (long)order[t] : t;
+  const double qx = (double)queries[q * 3], qy = (double)queries[q * 3 + 1], qz = (double)queries[q * 3 + 2];
+  long long at = offsets[q];
+  const long long end = offsets[q + 1] < (long long)total ? offsets[q + 1] : (long long)total;
+  if (at < 0) return;
+  for_each_in_range(g, qx, qy, qz, reach, r2_bits, [&](long j, long long, double, double, double) {
+    if (at < end) indices[at++] = g.index[j];
+  });
+}
+
 int check_grid(const void* a, const void* b, const void* c, long n, double ox, double oy, double oz, double cell, long ex, long ey, long ez) {
   if (!a || !b || !c || n <= 0) return CG_ERR_ARG;
   if (n > (long)INT_MAX) return CG_ERR_UNSUPPORTED;         // original indices are i32
@@ -275,4 +431,43 @@ extern "C" int cg_grid_count_within(const double* sorted_points, const int* sort
   if (st != CG_OK) return st;
   const Grid g = {sorted_points, sorted_index, sorted_keys, n, origin_x, origin_y, origin_z, cell, ext_x, ext_y, ext_z};
   return launch_query<false>(g, queries, queries_f64, query_order, m, radius, count, nullptr, stream);
+}
+
+extern "C" int cg_grid_nearest(const double* sorted_points, const int* sorted_index, const long long* sorted_keys, long n, double origin_x,
+                               double origin_y, double origin_z, double cell, long ext_x, long ext_y, long ext_z, const void* queries,
+                               int queries_f64, const int* query_order, long m, int* nn_index, double* nn_d2, int* rounds, void* stream) {
+  if (!queries || !nn_index || !nn_d2 || m <= 0) return CG_ERR_ARG;
+  if (m > (long)INT_MAX) return CG_ERR_UNSUPPORTED;
+  const int st = check_grid(sorted_points, sorted_index, sorted_keys, n, origin_x, origin_y, origin_z, cell, ext_x, ext_y, ext_z);
+  if (st != CG_OK) return st;
+  const Grid g = {sorted_points, sorted_index, sorted_keys, n, origin_x, origin_y, origin_z, cell, ext_x, ext_y, ext_z};
+  const unsigned blocks = (unsigned)((m + NB_Q_THREADS - 1) / NB_Q_THREADS);
+  if (queries_f64)
+    hipLaunchKernelGGL(grid_nearest_kernel<double>, dim3(blocks), dim3(NB_Q_THREADS), 0, (hipStream_t)stream, g, (const double*)queries,
+                       query_order, m, nn_index, nn_d2, rounds);
+  else
+    hipLaunchKernelGGL(grid_nearest_kernel<float>, dim3(blocks), dim3(NB_Q_THREADS), 0, (hipStream_t)stream, g, (const float*)queries,
+                       query_order, m, nn_index, nn_d2, rounds);
+  return cg_hip_status(hipGetLastError());
+}
+
+extern "C" int cg_grid_ball_fill(const double* sorted_points, const int* sorted_index, const long long* sorted_keys, long n, double origin_x,
+                                 double origin_y, double origin_z, double cell, long ext_x, long ext_y, long ext_z, const void* queries,
+                                 int queries_f64, const int* query_order, long m, double radius, const long long* offsets, long total,
+                                 int* indices, void* stream) {
+  if (!queries || !offsets || m <= 0 || total < 0 || (!indices && total > 0)) return CG_ERR_ARG;
+  if (m > (long)INT_MAX) return CG_ERR_UNSUPPORTED;
+  int st = check_grid(sorted_points, sorted_index, sorted_keys, n, origin_x, origin_y, origin_z, cell, ext_x, ext_y, ext_z);
+  if (st == CG_OK) st = check_radius(radius, cell);
+  if (st != CG_OK) return st;
+  if (total == 0) return CG_OK;
+  const Grid g = {sorted_points, sorted_index, sorted_keys, n, origin_x, origin_y, origin_z, cell, ext_x, ext_y, ext_z};
+  const unsigned blocks = (unsigned)((m + NB_Q_THREADS - 1) / NB_Q_THREADS);
+  if (queries_f64)
+    hipLaunchKernelGGL(grid_ball_fill_kernel<double>, dim3(blocks), dim3(NB_Q_THREADS), 0, (hipStream_t)stream, g, (const double*)queries,
+                       query_order, m, reach_of(radius), bits_of(radius * radius), offsets, total, indices);
+  else
+    hipLaunchKernelGGL(grid_ball_fill_kernel<float>, dim3(blocks), dim3(NB_Q_THREADS), 0, (hipStream_t)stream, g, (const float*)queries,
+                       query_order, m, reach_of(radius), bits_of(radius * radius), offsets, total, indices);
+  return cg_hip_status(hipGetLastError());
 }

@@ -11,7 +11,16 @@ lattice of `cell`-sized cells (cell >= radius): one 63-bit key per point, the po
 sort, a query answered from the few cells around it (csrc/grid_index.hip; ABI and semantics: include/catgrasp_amd_neighbors.h).  The
 cells only decide where the kernels look: no result depends on `cell`.  The normals have the pinned semantics of
 cg_organized_normals with "pixel index" read as "point index" and share its code after the search, so on a depth image's used points
-they are the same bits (tests/test_neighbors_gpu.py)."""
+they are the same bits (tests/test_neighbors_gpu.py).
+
+                                             .nearest(query)                         cKDTree.query(x), no distance_upper_bound
+                                             .ball_point(query, radius)              cKDTree.query_ball_point(x, r)
+    data    ->  cKDTree(data)            ->  .query(x) / .query_ball_point(x, r)     scipy.spatial.cKDTree at the reference's call shapes
+
+The unbounded nearest neighbour (include/catgrasp_amd_kdtree.h) searches boxes of doubling radius around the query and is exact:
+index for index the answer of the brute-force cg_nearest_neighbor, ties to the smaller index, whatever the cell.  `cKDTree` is the
+alias a port of the reference uses: `from catgrasp_amd.neighbors import cKDTree` (k = 1, Euclidean, exact: all the reference
+calls)."""
 import math
 import sys
 
@@ -161,6 +170,131 @@ class GridIndex:
                 _status(L.lib().cg_grid_count_within(*self._grid(), _p(q), int(q.dtype == torch.float64), _p(order), m, radius, _p(count),
                                                      _stream()), 'cg_grid_count_within')
         return count
+
+
+    def nearest(self, query, debug=False):
+        """Per query point the closest indexed point, unbounded and exact (cg_grid_nearest) -> (index (M) int32, d^2 (M) float64); exact
+        ties go to the smaller index.  Without an indexed point: (-1, +inf).  With debug=True also rounds (M) int32: the number of box
+        rounds the query took, negated where the linear pass finished it."""
+        q, m, order = self._queries(query)
+        idx = torch.full((m,), -1, dtype=torch.int32, device=self.device)
+        d2 = torch.full((m,), math.inf, dtype=torch.float64, device=self.device)
+        rounds = torch.zeros((m,), dtype=torch.int32, device=self.device) if debug else None
+        if order is not None:
+            with torch.cuda.device(self.device):
+                _status(L.lib().cg_grid_nearest(*self._grid(), _p(q), int(q.dtype == torch.float64), _p(order), m, _p(idx), _p(d2), _p(rounds),
+                                                _stream()), 'cg_grid_nearest')
+        return (idx, d2, rounds) if debug else (idx, d2)
+
+    def ball_point(self, query, radius):
+        """Per query point the indexed points within `radius` (cg_grid_count_within, cg_grid_ball_fill) -> (offsets (M + 1) int64,
+        indices int32): the neighbours of query i are indices[offsets[i]:offsets[i + 1]], in ascending original index."""
+        radius = self._radius(radius)
+        q, m, order = self._queries(query)
+        offsets = torch.zeros((m + 1,), dtype=torch.int64, device=self.device)
+        if order is None:
+            return offsets, torch.empty((0,), dtype=torch.int32, device=self.device)
+        count = torch.empty((m,), dtype=torch.int32, device=self.device)
+        grid, f64 = self._grid(), int(q.dtype == torch.float64)
+        with torch.cuda.device(self.device):
+            _status(L.lib().cg_grid_count_within(*grid, _p(q), f64, _p(order), m, radius, _p(count), _stream()), 'cg_grid_count_within')
+            offsets[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+            total = int(offsets[-1])
+            indices = torch.empty((total,), dtype=torch.int32, device=self.device)
+            _status(L.lib().cg_grid_ball_fill(*grid, _p(q), f64, _p(order), m, radius, _p(offsets), total, _p(indices), _stream()),
+                    'cg_grid_ball_fill')
+        # the kernel fills a segment in scan order: sort by (query, index), one key each (m n < 2^62)
+        owner = torch.repeat_interleave(torch.arange(m, device=self.device), count.long(), output_size=total)
+        key = torch.sort(owner * self.n + indices.long()).values
+        return offsets, (key - owner * self.n).to(torch.int32)
+
+
+def default_cell(lo, hi, n):
+    """The cell cKDTree indexes a cloud with when none is given: the pitch at which an occupied cell holds about 4 points, for a cloud
+    that fills its bounding box (cbrt(4 V / n)), one that is a surface in it (sqrt(4 A / n), A the product of the two largest
+    extents) or a line (4 L / n), whichever is largest; 1 for a cloud without extent.  It decides speed only: no result depends on it."""
+    e = sorted((float(h) - float(l) for l, h in zip(lo, hi)), reverse=True)
+    n = max(int(n), 1)
+    cell = max((4.0 * e[0] * e[1] * e[2] / n) ** (1.0 / 3.0), math.sqrt(4.0 * e[0] * e[1] / n), 4.0 * e[0] / n)
+    return cell if math.isfinite(cell) and cell * cell >= sys.float_info.min else 1.0
+
+
+class cKDTree:
+    """scipy.spatial.cKDTree at the calls the reference makes, on the grid index: `cKDTree(data).query(x)`,
+    `.query(x, distance_upper_bound=r)`, `.query_ball_point(x, r[, return_length=True])`; `.n`, `.m` (3) and `.data` as scipy has them.
+    data: (N, 3) float32 or float64, array or tensor.  cell: the pitch of the index, default_cell() of the data unless given; it decides
+    speed only.  Exact: k = 1, the Euclidean metric, eps = 0 -- the reference asks nothing else, and anything else raises
+    NotImplementedError.  Exact ties go to the smaller index (scipy does not state its rule)."""
+
+    m = 3
+
+    def __init__(self, data, cell=None, device=None):
+        pts = _cloud(data, 'data')
+        self.n = int(pts.shape[0])
+        self.data = pts.cpu().numpy()
+        if cell is None:
+            cell = default_cell(self.data.min(axis=0), self.data.max(axis=0), self.n) if self.n else 1.0
+        self.index = GridIndex(pts, cell, device=device)
+        self.device = self.index.device
+        self._wider = {}                                              # radius -> the GridIndex with that cell, for query_ball_point beyond the cell
+
+    def _points(self, x, what):
+        """-> ((M, 3) cloud, whether x was one point)"""
+        if not torch.is_tensor(x):
+            x = np.asarray(x)
+            if x.dtype not in (np.float32, np.float64):
+                x = x.astype(np.float64)
+        single = x.ndim == 1
+        return _cloud(x.reshape(1, -1) if single else x, what), single
+
+    def query(self, x, k=1, eps=0, p=2, distance_upper_bound=math.inf, return_tensor=False):
+        """-> (distances float64, indices int64) of the nearest point of data per row of x, numpy arrays unless return_tensor; scalars
+        for a single point (3,).  Without a point within distance_upper_bound (d <= bound counts as within): (inf, n)."""
+        if k != 1 or p != 2 or eps != 0:
+            raise NotImplementedError(f'cKDTree.query: only k=1, p=2, eps=0 are built (the reference uses nothing else); got k={k!r}, p={p!r}, '
+                                      f'eps={eps!r}')
+        bound = float(distance_upper_bound)
+        if not bound >= 0:
+            raise ValueError(f'distance_upper_bound must be >= 0, got {distance_upper_bound!r}')
+        q, single = self._points(x, 'x')
+        if bound <= self.index.cell and bound * bound >= sys.float_info.min:
+            idx, d2 = self.index.nearest_within(q, bound)
+        else:
+            idx, d2 = self.index.nearest(q)
+            if math.isfinite(bound):
+                miss = ~(d2 <= bound * bound)
+                idx, d2 = idx.masked_fill(miss, -1), d2.masked_fill(miss, math.inf)
+        idx = idx.long()
+        dist, idx = torch.sqrt(d2), torch.where(idx < 0, self.n, idx)
+        if single:
+            dist, idx = dist[0], idx[0]
+        if return_tensor:
+            return dist, idx
+        return (float(dist), int(idx)) if single else (dist.cpu().numpy(), idx.cpu().numpy())
+
+    def query_ball_point(self, x, r, p=2, eps=0, return_length=False):
+        """-> per row of x the indices of the points of data within r (d <= r), ascending: an object array of lists, or the lengths
+        with return_length; for a single point (3,) one list or one number.  A radius above the index's cell builds a second index with
+        cell = r, which is kept for the next call."""
+        if p != 2 or eps != 0:
+            raise NotImplementedError(f'cKDTree.query_ball_point: only p=2, eps=0 are built (the reference uses nothing else); got p={p!r}, '
+                                      f'eps={eps!r}')
+        r = _positive(r, 'r')
+        q, single = self._points(x, 'x')
+        index = self.index
+        if r > index.cell:
+            index = self._wider.get(r)
+            if index is None:
+                index = self._wider[r] = GridIndex(self.data, r, device=self.device)
+        if return_length:
+            count = index.count_within(q, r).cpu().numpy().astype(np.intp)
+            return int(count[0]) if single else count
+        offsets, indices = index.ball_point(q, r)
+        offsets, indices = offsets.cpu().tolist(), indices.cpu().tolist()
+        out = np.empty((len(offsets) - 1,), dtype=object)
+        for i in range(len(out)):
+            out[i] = indices[offsets[i]:offsets[i + 1]]
+        return out[0] if single else out
 
 
 def estimate_normals(xyz, radius=0.002, max_nn=30, view_point=(0, 0, 0), device=None, return_tensor=False, debug=False):
