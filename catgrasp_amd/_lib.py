@@ -17,8 +17,9 @@ include/catgrasp_amd_pointgroup.h, described by `pointgroup_signatures()`, and t
 fifth, include/catgrasp_amd_scene.h, described by `scene_signatures()`, and the grid index (neighbour queries and normals of any cloud)
 a sixth, include/catgrasp_amd_neighbors.h, described by `neighbors_signatures()`, and the k-d tree searches on that index (unbounded
 nearest neighbour, ball lists) a seventh, include/catgrasp_amd_kdtree.h, described by `kdtree_signatures()`, and the gradients of the
-sparse convolution layers an eighth, include/catgrasp_amd_sparse_grad.h, described by `sparse_grad_signatures()`.  `lib()` binds and
-requires all eight.
+sparse convolution layers an eighth, include/catgrasp_amd_sparse_grad.h, described by `sparse_grad_signatures()`, and BatchNorm in
+batch-statistics mode with ReLU (forward and backward) a ninth, include/catgrasp_amd_bn.h, described by `bn_signatures()`.  `lib()`
+binds and requires all nine.
 """
 import ctypes
 import os
@@ -36,6 +37,7 @@ SCENE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_scene.h') 
 NEIGHBORS_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_neighbors.h')   # the grid index: likewise
 KDTREE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_kdtree.h')   # the k-d tree searches on the grid index: likewise
 SPARSE_GRAD_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_sparse_grad.h')   # the sparse layers' gradients: likewise
+BN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_bn.h')   # batch-statistics BatchNorm + ReLU: likewise
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -123,6 +125,12 @@ def sparse_grad_signatures():
         return signatures(f.read())
 
 
+def bn_signatures():
+    """signatures() of include/catgrasp_amd_bn.h: same parser, same type mapping."""
+    with open(BN_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -132,7 +140,7 @@ def lib():
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
         sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures(),
-                **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures()}
+                **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')

@@ -51,8 +51,9 @@ def _prologue(bn):
     return kept[1]
 
 
-def _subm3(cin, cout, key):
-    return spconv.SubMConv3d(cin, cout, kernel_size=3, padding=1, bias=True, indice_key=key)
+def _subm3(cin, cout, key, layers=spconv):
+    """layers: the module that supplies the three sparse layer classes -- `spconv`, or its drop-in with gradients."""
+    return layers.SubMConv3d(cin, cout, kernel_size=3, padding=1, bias=True, indice_key=key)
 
 
 def _pre_activated(norm_fn, width, conv):
@@ -64,12 +65,12 @@ class ResidualBlock(SparseModule):
     """i_branch (identity, or a k = 1 convolution when the widths differ) + conv_branch (two pre-activated k = 3 convolutions).
     Eval mode: 2 launches, 3 with an i_branch."""
 
-    def __init__(self, in_channels, out_channels, norm_fn, indice_key=None):
+    def __init__(self, in_channels, out_channels, norm_fn, indice_key=None, layers=spconv):
         super().__init__()
-        shortcut = nn.Identity() if in_channels == out_channels else spconv.SubMConv3d(in_channels, out_channels, kernel_size=1, bias=True)
+        shortcut = nn.Identity() if in_channels == out_channels else layers.SubMConv3d(in_channels, out_channels, kernel_size=1, bias=True)
         self.i_branch = spconv.SparseSequential(shortcut)
-        self.conv_branch = spconv.SparseSequential(*_pre_activated(norm_fn, in_channels, _subm3(in_channels, out_channels, indice_key)),
-                                                   *_pre_activated(norm_fn, out_channels, _subm3(out_channels, out_channels, indice_key)))
+        self.conv_branch = spconv.SparseSequential(*_pre_activated(norm_fn, in_channels, _subm3(in_channels, out_channels, indice_key, layers)),
+                                                   *_pre_activated(norm_fn, out_channels, _subm3(out_channels, out_channels, indice_key, layers)))
 
     def forward(self, input, features_b=None):
         """features_b: the block reads [input.features | features_b] (the block behind a skip)."""
@@ -88,9 +89,9 @@ class ResidualBlock(SparseModule):
 class VGGBlock(SparseModule):
     """One pre-activated k = 3 convolution: 1 launch."""
 
-    def __init__(self, in_channels, out_channels, norm_fn, indice_key=None):
+    def __init__(self, in_channels, out_channels, norm_fn, indice_key=None, layers=spconv):
         super().__init__()
-        self.conv_layers = spconv.SparseSequential(*_pre_activated(norm_fn, in_channels, _subm3(in_channels, out_channels, indice_key)))
+        self.conv_layers = spconv.SparseSequential(*_pre_activated(norm_fn, in_channels, _subm3(in_channels, out_channels, indice_key, layers)))
 
     def forward(self, input, features_b=None):
         bn, _, conv = self.conv_layers
@@ -102,22 +103,22 @@ class UBlock(nn.Module):
     level `u`, `deconv` (its inverse) and `blocks_tail`, whose first block reads [this level's output | the decoder's] and narrows
     the doubled width back.  Rule books: 'subm<id>' for every block of the level, 'spconv<id>' for conv and deconv."""
 
-    def __init__(self, nPlanes, norm_fn, block_reps, block, indice_key_id=1):
+    def __init__(self, nPlanes, norm_fn, block_reps, block, indice_key_id=1, layers=spconv):
         super().__init__()
         self.nPlanes = nPlanes
         width, subm, strided = nPlanes[0], f'subm{indice_key_id}', f'spconv{indice_key_id}'
 
         def group(first_in):
             return spconv.SparseSequential(OrderedDict(
-                (f'block{i}', block(first_in if i == 0 else width, width, norm_fn, indice_key=subm)) for i in range(block_reps)))
+                (f'block{i}', block(first_in if i == 0 else width, width, norm_fn, indice_key=subm, layers=layers)) for i in range(block_reps)))
         self.blocks = group(width)
         if len(nPlanes) > 1:
             below = nPlanes[1]
             self.conv = spconv.SparseSequential(*_pre_activated(
-                norm_fn, width, spconv.SparseConv3d(width, below, kernel_size=2, stride=2, bias=True, indice_key=strided)))
-            self.u = UBlock(nPlanes[1:], norm_fn, block_reps, block, indice_key_id=indice_key_id + 1)
+                norm_fn, width, layers.SparseConv3d(width, below, kernel_size=2, stride=2, bias=True, indice_key=strided)))
+            self.u = UBlock(nPlanes[1:], norm_fn, block_reps, block, indice_key_id=indice_key_id + 1, layers=layers)
             self.deconv = spconv.SparseSequential(*_pre_activated(
-                norm_fn, below, spconv.SparseInverseConv3d(below, width, kernel_size=2, bias=True, indice_key=strided)))
+                norm_fn, below, layers.SparseInverseConv3d(below, width, kernel_size=2, bias=True, indice_key=strided)))
             self.blocks_tail = group(2 * width)
 
     def forward(self, input):
@@ -149,7 +150,8 @@ _KEPT = {'cluster_radius': 'cluster_radius', 'cluster_meanActive': 'cluster_mean
 
 
 class PointGroup(nn.Module):
-    def __init__(self, cfg):
+    def __init__(self, cfg, layers=spconv):
+        """layers: see _subm3; `pointgroup_train.PointGroup` passes the layers with gradients."""
         super().__init__()
         self.cfg = cfg
         for own, theirs in _KEPT.items():
@@ -162,12 +164,12 @@ class PointGroup(nn.Module):
         norm_fn = functools.partial(nn.BatchNorm1d, eps=1e-5, momentum=0.1)
         block = ResidualBlock if cfg.block_residual else VGGBlock
 
-        self.input_conv = spconv.SparseSequential(_subm3(channels, m, 'subm1'))
-        self.unet = UBlock([m * level for level in range(1, 8)], norm_fn, cfg.block_reps, block, indice_key_id=1)
+        self.input_conv = spconv.SparseSequential(_subm3(channels, m, 'subm1', layers))
+        self.unet = UBlock([m * level for level in range(1, 8)], norm_fn, cfg.block_reps, block, indice_key_id=1, layers=layers)
         self.output_layer = spconv.SparseSequential(norm_fn(m), nn.ReLU())
         self.offset = nn.Sequential(nn.Linear(m, m), norm_fn(m), nn.ReLU(), nn.Linear(m, 3))
         # the score branch: never run here (forward), constructed because checkpoints hold its tensors and load strictly
-        self.score_unet = UBlock([m, 2 * m], norm_fn, 2, block, indice_key_id=1)
+        self.score_unet = UBlock([m, 2 * m], norm_fn, 2, block, indice_key_id=1, layers=layers)
         self.score_outputlayer = spconv.SparseSequential(norm_fn(m), nn.ReLU())
         self.score_linear = nn.Linear(m, 1)
         self.apply(self.set_bn_init)
