@@ -5,7 +5,8 @@
 //                  closed triangle of A meets some closed triangle of B".  Here: both meshes posed into the common frame with the
 //                  fma chain of the mesh/cloud path, one thread per triangle of A, B's posed triangles and boxes staged through LDS
 //                  a chunk at a time, box reject, then a 17-axis float32 separating-axis test (2 normals, 9 edge x edge, 6 in-plane
-//                  edge normals -- the last six decide coplanar pairs, where the cross products degenerate).
+//                  edge normals -- the last six decide coplanar pairs, where the cross products degenerate; a zero-area face gets
+//                  three more, see tri_tri_overlap).
 //   cloud / cloud: two fcl::OcTree (collision_manager.cpp:63-70): occupied leaf cube against occupied leaf cube, each set in its own
 //                  pose: cube of A (axis-aligned in A's frame) against the cube of B carried into A's frame by inv(pose A) pose B --
 //                  the 15-axis box/box separating-axis test FCL's box-box narrow phase is built on, float32.
@@ -58,6 +59,17 @@ __device__ __forceinline__ bool tri_tri_overlap(const float* P, const float* Q) 
     for (int j = 0; j < 3; ++j) { float L[3]; cross3(ep[i], eq[j], L); axis(L); }
 #pragma unroll
   for (int i = 0; i < 3; ++i) { float L[3]; cross3(np_, ep[i], L); axis(L); cross3(nq, eq[i], L); axis(L); }
+  // a zero-area face (a closed segment or a point) has no normal: every axis above that is built from it is the zero vector, and a
+  // segment that lies in the other face's plane is left with that face's three edge normals only.  Its own in-plane normal comes
+  // from the OTHER face's normal.  Proper pairs never get here, so their verdicts are what the 17 axes say.
+  if (np_[0] == 0.f && np_[1] == 0.f && np_[2] == 0.f) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { float L[3]; cross3(nq, ep[i], L); axis(L); }
+  }
+  if (nq[0] == 0.f && nq[1] == 0.f && nq[2] == 0.f) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { float L[3]; cross3(np_, eq[i], L); axis(L); }
+  }
   return !sep;
 }
 

@@ -503,9 +503,13 @@ static int seg_tri64(const double* a, const double* b, const double (*v)[3], con
     double S[2][2] = {{a[u], a[w]}, {b[u], b[w]}};
     return overlap2d(S, 2, T, 3);
   }
-  const double t = da / (da - db);
-  double X[1][2] = {{a[u] + t * (b[u] - a[u]), a[w] + t * (b[w] - a[w])}};
-  return overlap2d(X, 1, T, 3);
+  /* the crossing point X = a + da / (da - db) (b - a), with X and the triangle both scaled by D = da - db: no division, so that a
+   * crossing point ON an edge of the triangle stays on it (lattice inputs: every term is exact in float64) */
+  const double D = da - db;
+  double X[1][2] = {{a[u] * D + da * (b[u] - a[u]), a[w] * D + da * (b[w] - a[w])}};
+  double TD[3][2];
+  for (int i = 0; i < 3; ++i) { TD[i][0] = T[i][0] * D; TD[i][1] = T[i][1] * D; }
+  return overlap2d(X, 1, TD, 3);
 }
 
 int cr_tri_tri_overlap64(const float* Pf, const float* Qf) {
