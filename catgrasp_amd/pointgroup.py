@@ -15,6 +15,9 @@ instead of through SparseSequential:
                            launches on the voxel rows (16 -> 16 with output_layer's BatchNorm + ReLU as prologue, 16 -> 3 with the head's
                            own), then one 3-float row gather by input_map.
 
+The blocks' and UBlock's forward are the only walk of the module tree (block order, skip, residual, recursion).  They take `run`,
+how one `BatchNorm1d, ReLU, conv` is executed: `_fused` by default, `pointgroup_train._train_run` for a training step.
+
 At the shipped configuration (m = 16, block_reps = 2, residual blocks) that is 71 + 2 launches and 19 rule-book builds (7 submanifold,
 6 strided, 6 inverse).  The score branch (epoch > prepare_epochs) draws torch.rand and is training-time only: it is constructed, for the
 checkpoint's keys, and not run."""
@@ -51,6 +54,13 @@ def _prologue(bn):
     return kept[1]
 
 
+def _fused(input, bn, relu, conv, residual=None, features_b=None):
+    """How the walk (the blocks' and UBlock's forward) runs one `BatchNorm1d, ReLU, conv`: the one decision in which the eval-mode
+    and the training forward differ, taken as the walk's `run` argument.  This is the eval-mode run, one launch; the training
+    one is pointgroup_train._train_run."""
+    return conv(input, prologue=_prologue(bn), residual=residual, features_b=features_b)
+
+
 def _subm3(cin, cout, key, layers=spconv):
     """layers: the module that supplies the three sparse layer classes -- `spconv`, or its drop-in with gradients."""
     return layers.SubMConv3d(cin, cout, kernel_size=3, padding=1, bias=True, indice_key=key)
@@ -72,18 +82,18 @@ class ResidualBlock(SparseModule):
         self.conv_branch = spconv.SparseSequential(*_pre_activated(norm_fn, in_channels, _subm3(in_channels, out_channels, indice_key, layers)),
                                                    *_pre_activated(norm_fn, out_channels, _subm3(out_channels, out_channels, indice_key, layers)))
 
-    def forward(self, input, features_b=None):
-        """features_b: the block reads [input.features | features_b] (the block behind a skip)."""
-        bn0, _, conv0, bn1, _, conv1 = self.conv_branch
+    def forward(self, input, features_b=None, run=_fused):
+        """features_b: the block reads [input.features | features_b] (the block behind a skip).  run: see _fused."""
+        bn0, relu0, conv0, bn1, relu1, conv1 = self.conv_branch
         shortcut = self.i_branch[0]
-        hidden = conv0(input, prologue=_prologue(bn0), features_b=features_b)
         if isinstance(shortcut, nn.Identity):
             if features_b is not None:
                 raise ValueError('a block of equal widths has one source')
             residual = input.features
         else:
             residual = shortcut(input, features_b=features_b).features
-        return conv1(hidden, prologue=_prologue(bn1), residual=residual)
+        hidden = run(input, bn0, relu0, conv0, features_b=features_b)
+        return run(hidden, bn1, relu1, conv1, residual=residual)
 
 
 class VGGBlock(SparseModule):
@@ -93,9 +103,8 @@ class VGGBlock(SparseModule):
         super().__init__()
         self.conv_layers = spconv.SparseSequential(*_pre_activated(norm_fn, in_channels, _subm3(in_channels, out_channels, indice_key, layers)))
 
-    def forward(self, input, features_b=None):
-        bn, _, conv = self.conv_layers
-        return conv(input, prologue=_prologue(bn), features_b=features_b)
+    def forward(self, input, features_b=None, run=_fused):
+        return run(input, *self.conv_layers, features_b=features_b)
 
 
 class UBlock(nn.Module):
@@ -121,25 +130,21 @@ class UBlock(nn.Module):
                 norm_fn, below, layers.SparseInverseConv3d(below, width, kernel_size=2, bias=True, indice_key=strided)))
             self.blocks_tail = group(2 * width)
 
-    def forward(self, input):
+    def forward(self, input, run=_fused, cat_skip=False):
+        """run: see _fused.  cat_skip: the skip is one torch.cat whatever USE_TWO_SOURCE_KERNEL says (the two-source kernel has
+        no gradient)."""
         output = input
         for blk in self.blocks:
-            output = blk(output)
+            output = blk(output, run=run)
         if len(self.nPlanes) > 1:
-            bn, _, conv = self.conv
-            decoder = self.u(conv(output, prologue=_prologue(bn)))
-            bn, _, deconv = self.deconv
-            decoder = deconv(decoder, prologue=_prologue(bn))
+            decoder = run(self.u(run(output, *self.conv), run, cat_skip), *self.deconv)
             first, *rest = self.blocks_tail
-            if USE_TWO_SOURCE_KERNEL:
-                output = first(output, features_b=decoder.features)
+            if USE_TWO_SOURCE_KERNEL and not cat_skip:
+                output = first(output, features_b=decoder.features, run=run)
             else:
-                both = spconv.SparseConvTensor(torch.cat((output.features, decoder.features), dim=1), output.indices, output.spatial_shape,
-                                               output.batch_size)
-                both.indice_dict, both.grid = output.indice_dict, output.grid
-                output = first(both)
+                output = first(output.replace_feature(torch.cat((output.features, decoder.features), dim=1)), run=run)
             for blk in rest:
-                output = blk(output)
+                output = blk(output, run=run)
         return output
 
 
@@ -200,8 +205,7 @@ class PointGroup(nn.Module):
         """offset(output_layer(.)) per voxel row: (M, m) -> (M, 3) in two K = 1 launches."""
         self._refuse_training()
         with torch.no_grad():
-            n = voxel_features.shape[0]
-            rows = torch.arange(n, dtype=torch.int32, device=voxel_features.device).view(n, 1)
+            rows = spconv.identity_rules(voxel_features.shape[0], voxel_features.device)
             lin0, bn, lin1 = self.offset[0], self.offset[1], self.offset[3]
             scale, shift = _prologue(self.output_layer[0])
             hidden = spconv.sparse_conv(voxel_features, rows, lin0.weight.detach().t().unsqueeze(0), lin0.bias.detach(), scale, shift)

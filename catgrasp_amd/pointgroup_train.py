@@ -5,7 +5,8 @@ offset loss and model_fn, :310-389), so that the checkpoints `PointGroupPredicto
 and shapes, same initial tensors under the same torch.manual_seed, so `pointgroup.load_model` loads what it saves, strictly.
 
   eval mode       the base class's fused forward, bit for bit.
-  training mode   every `BatchNorm1d, ReLU, conv` run is bn_relu_train (batch statistics, csrc/batchnorm_train.hip) followed by the
+  training mode   the base class's walk of the U-Net (UBlock.forward and the blocks') with _train_run in place of the fused launch:
+                  every `BatchNorm1d, ReLU, conv` run is bn_relu_train (batch statistics, csrc/batchnorm_train.hip) followed by the
                   layer's SparseConvFunction; residuals are torch adds, skips torch.cat.  The head runs per point after the gather, as
                   the reference's does: the batch statistics of offset.1 run over the N points, not over the M voxels.  The two
                   nn.Linear are K = 1 SparseConvFunction calls, the gather is GatherRows, whose backward is the sum-mode voxelization
@@ -68,8 +69,7 @@ def gather_rows(features, input_map, v2p_map=None):
 
 def _linear(x, lin):
     """nn.Linear as a K = 1 layer, so that its gradients are cg_sparse_conv_wgrad's and cg_sparse_conv_dgrad's chains."""
-    n = x.shape[0]
-    rows = torch.arange(n, dtype=torch.int32, device=x.device).view(n, 1)
+    rows = spconv.identity_rules(x.shape[0], x.device)
     return spconv.SparseConvFunction.apply(x, lin.weight.t().unsqueeze(0), lin.bias, rows, rows, False)
 
 
@@ -79,34 +79,10 @@ def _bn_relu(x, bn, relu):
     return bn_relu_train(x, bn)
 
 
-def _pre_activated(input, bn, relu, conv, residual=None):
-    """One `BatchNorm1d, ReLU, conv` run in training mode."""
-    active = spconv.SparseConvTensor(_bn_relu(input.features, bn, relu), input.indices, input.spatial_shape, input.batch_size)
-    active.indice_dict, active.grid = input.indice_dict, input.grid
-    return conv(active, residual=residual)
-
-
-def _block(block, input):
-    if isinstance(block, pointgroup.VGGBlock):
-        return _pre_activated(input, *block.conv_layers)
-    shortcut = block.i_branch[0]
-    residual = input.features if isinstance(shortcut, nn.Identity) else shortcut(input).features
-    bn0, relu0, conv0, bn1, relu1, conv1 = block.conv_branch
-    return _pre_activated(_pre_activated(input, bn0, relu0, conv0), bn1, relu1, conv1, residual=residual)
-
-
-def _ublock(u, input):
-    output = input
-    for blk in u.blocks:
-        output = _block(blk, output)
-    if len(u.nPlanes) > 1:
-        decoder = _pre_activated(_ublock(u.u, _pre_activated(output, *u.conv)), *u.deconv)
-        both = spconv.SparseConvTensor(torch.cat((output.features, decoder.features), dim=1), output.indices, output.spatial_shape, output.batch_size)
-        both.indice_dict, both.grid = output.indice_dict, output.grid
-        output = both
-        for blk in u.blocks_tail:
-            output = _block(blk, output)
-    return output
+def _train_run(input, bn, relu, conv, residual=None, features_b=None):
+    """One `BatchNorm1d, ReLU, conv` run in training mode: the `run` of pointgroup's walk (pointgroup._fused is the eval-mode one).
+    The walk is asked for torch.cat skips, so features_b stays None; a layer with gradients refuses anything else."""
+    return conv(input.replace_feature(_bn_relu(input.features, bn, relu)), residual=residual, features_b=features_b)
 
 
 class PointGroup(pointgroup.PointGroup):
@@ -120,7 +96,7 @@ class PointGroup(pointgroup.PointGroup):
             return super().forward(input_tensor, input_map, coords, batch_idxs, batch_offsets, epoch)
         if epoch > self.prepare_epochs:
             raise NotImplementedError('the score branch (epoch > prepare_epochs) is not built')
-        output = _ublock(self.unet, self.input_conv[0](input_tensor))
+        output = self.unet(self.input_conv[0](input_tensor), run=_train_run, cat_skip=True)
         bn, relu = self.output_layer
         lin0, head_bn, head_relu, lin1 = self.offset
         voxel_feats = _bn_relu(output.features, bn, relu)

@@ -72,6 +72,14 @@ class SparseConvTensor(object):
     def find_indice_pair(self, key):
         return None if key is None else self.indice_dict.get(key)
 
+    def replace_feature(self, features, indices=None, spatial_shape=None):
+        """This tensor's bookkeeping with other features: the result shares `indice_dict` (so the rule books below are found, not
+        rebuilt) and `grid`.  Same sites unless `indices` and `spatial_shape` are given (a layer whose output sites differ)."""
+        res = SparseConvTensor(features, self.indices if indices is None else indices,
+                               self.spatial_shape if spatial_shape is None else spatial_shape, self.batch_size, self.grid)
+        res.indice_dict = self.indice_dict
+        return res
+
     def dense(self, channels_first=True):
         """(batch, C, s0, s1, s2), zeros at inactive sites ((batch, s0, s1, s2, C) if not channels_first)."""
         out = torch.zeros([self.batch_size] + self.spatial_shape + [self.features.shape[1]], dtype=self.features.dtype,
@@ -115,6 +123,11 @@ def _sorted_keys(indices, spatial_shape, batch_size, err):
     check(L.lib().cg_sparse_keys(_p(indices), n, batch_size, *spatial_shape, 0, _p(keys), _p(err), _stream()), 'cg_sparse_keys')
     _raise_flag(err, 'sparse tensor')
     return torch.sort(keys, stable=True)
+
+
+def identity_rules(n, device):
+    """Rule book of a K = 1 layer (SubMConv3d(k=1), nn.Linear as a layer): nbr (n, 1), every row reads itself."""
+    return torch.arange(n, dtype=torch.int32, device=device).view(n, 1)
 
 
 def subm_rules(indices, spatial_shape, batch_size):
@@ -254,8 +267,7 @@ class SparseConvolution(SparseModule):
     def _rule_book(self, input):
         """-> (nbr, output indices, output spatial shape)"""
         if self.conv1x1:
-            n = input.indices.shape[0]
-            return torch.arange(n, dtype=torch.int32, device=input.indices.device).view(n, 1), input.indices, input.spatial_shape
+            return identity_rules(input.indices.shape[0], input.indices.device), input.indices, input.spatial_shape
         book = input.find_indice_pair(self.indice_key)
         if self.inverse:
             if book is None:
@@ -282,10 +294,7 @@ class SparseConvolution(SparseModule):
         K = nbr.shape[1]
         out = sparse_conv(feats, nbr, self.weight.detach().reshape(K, self.in_channels, self.out_channels), self.bias, scale, shift, residual,
                           None if features_b is None else features_b.detach().contiguous())
-        res = SparseConvTensor(out, out_indices, out_shape, input.batch_size)
-        res.indice_dict = input.indice_dict
-        res.grid = input.grid
-        return res
+        return input.replace_feature(out, out_indices, out_shape)
 
 
 class SubMConv3d(SparseConvolution):

@@ -37,7 +37,7 @@ from . import _lib as L
 from . import spconv as _S
 from ._lib import _p, _stream, check
 from .spconv import (MAX_CIN, MAX_COUT, RuleBook, SparseConvTensor, SparseConvolution, SparseModule, SparseSequential,  # noqa: F401
-                     bn_relu_prologue, down_rules, inverse_rules, sparse_conv, subm_rules)
+                     bn_relu_prologue, down_rules, identity_rules, inverse_rules, sparse_conv, subm_rules)
 
 
 def grad_rows():
@@ -151,10 +151,7 @@ class _Differentiable:
         out = SparseConvFunction.apply(feats, self.weight.reshape(nbr.shape[1], self.in_channels, self.out_channels), self.bias, nbr, nbr_t, flip)
         if residual is not None:
             out = out + residual
-        res = SparseConvTensor(out, out_indices, out_shape, input.batch_size)
-        res.indice_dict = input.indice_dict
-        res.grid = input.grid
-        return res
+        return input.replace_feature(out, out_indices, out_shape)
 
 
 class SubMConv3d(_Differentiable, _S.SubMConv3d):

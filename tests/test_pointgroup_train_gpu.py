@@ -21,7 +21,7 @@ from torch import nn
 import catgrasp_amd.spconv as base_spconv
 import pointgroup_ref as P
 import pointgroup_train_ref as T
-from catgrasp_amd import pointgroup, pointgroup_train
+from catgrasp_amd import _lib, pointgroup, pointgroup_train
 
 pytestmark = pytest.mark.gpu
 
@@ -129,6 +129,29 @@ def test_a_step_against_float64_under_the_devices_masks(kind, cuda_device, monke
     assert pt_offsets.shape == (len(P.scene(kind)) + 40, 3) and pt_offsets.dtype == torch.float32
     _check_step(kind, masks, loss, pt_offsets, grads, model.state_dict(), 'fused')
     assert all(int(v) == 0 for k, v in model.state_dict().items() if k.startswith('score_') and k.endswith('num_batches_tracked'))
+
+
+def test_launch_counts_of_one_training_forward(cuda_device, monkeypatch):
+    """One training forward on scene n33 (33 voxels, the smallest scene whose every level keeps more than one row): 73 cg_sparse_conv
+    launches (input_conv, the 70 layers of the U-Net, the two nn.Linear of the head) and 66 cg_bn_relu_train_forward calls (the 64
+    BatchNorms of the U-Net, output_layer's and offset.1), never the two-source kernel.  Both figures were counted at commit 55cfb43,
+    before the training forward became the inference model's walk with another `run`."""
+    model = _model(cuda_device)
+    lib = _lib.lib()
+    counts = {}
+
+    def counted(name):
+        fn = getattr(lib, name)
+
+        def call(*args):
+            counts[name] = counts.get(name, 0) + 1
+            return fn(*args)
+        monkeypatch.setattr(lib, name, call)
+    for name in ('cg_sparse_conv', 'cg_sparse_conv_cat', 'cg_bn_relu_train_forward'):
+        counted(name)
+    tensor, imap, coords, _, v2p = _inputs('n33', cuda_device)
+    model(tensor, imap, coords, None, None, 0, v2p_map=v2p)
+    assert counts == {'cg_sparse_conv': 73, 'cg_bn_relu_train_forward': 66}
 
 
 def test_the_torch_op_baseline_is_the_same_network(cuda_device, monkeypatch):

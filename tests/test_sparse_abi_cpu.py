@@ -168,3 +168,29 @@ def test_forward_without_a_hip_device_raises(monkeypatch):
     for layer in layers:
         with torch.no_grad(), pytest.raises((_lib.CatgraspAmdError, NotImplementedError)):
             layer(x)
+
+
+def test_replace_feature_shares_the_bookkeeping():
+    idx = torch.tensor([[0, 0, 0, 0], [0, 1, 1, 1], [1, 2, 2, 2]], dtype=torch.int32)
+    x = spconv.SparseConvTensor(torch.zeros(3, 16), idx, [9, 12, 17], 2, grid=object())
+    x.indice_dict['subm1'] = 'a rule book'
+    feats = torch.ones(3, 32)
+    y = x.replace_feature(feats)                                            # the same sites by default
+    assert y is not x and y.features is feats and x.features.shape == (3, 16)
+    assert y.indice_dict is x.indice_dict and y.grid is x.grid
+    assert y.indices is x.indices and y.spatial_shape == [9, 12, 17] and y.batch_size == 2
+    y.indice_dict['spconv1'] = 'another'                                    # a book built below is seen above
+    assert x.find_indice_pair('spconv1') == 'another'
+    out_idx, out_feats = torch.tensor([[0, 0, 0, 0], [1, 1, 1, 1]], dtype=torch.int32), torch.ones(2, 48)
+    z = x.replace_feature(out_feats, out_idx, (4, 6, 8))                    # a layer whose output sites differ
+    assert z.features is out_feats and z.indices is out_idx and z.spatial_shape == [4, 6, 8] and z.batch_size == 2
+    assert z.indice_dict is x.indice_dict and z.grid is x.grid
+    with pytest.raises(ValueError, match='rows'):
+        x.replace_feature(torch.ones(2, 16))
+
+
+@pytest.mark.parametrize('n', [0, 1, 5])
+def test_identity_rules_is_the_arange_column(n):
+    rows = spconv.identity_rules(n, torch.device('cpu'))
+    want = torch.arange(n, dtype=torch.int32, device=torch.device('cpu')).view(n, 1)
+    assert rows.dtype == torch.int32 and tuple(rows.shape) == (n, 1) and rows.device == want.device and torch.equal(rows, want)
