@@ -18,8 +18,9 @@ fifth, include/catgrasp_amd_scene.h, described by `scene_signatures()`, and the 
 a sixth, include/catgrasp_amd_neighbors.h, described by `neighbors_signatures()`, and the k-d tree searches on that index (unbounded
 nearest neighbour, ball lists) a seventh, include/catgrasp_amd_kdtree.h, described by `kdtree_signatures()`, and the gradients of the
 sparse convolution layers an eighth, include/catgrasp_amd_sparse_grad.h, described by `sparse_grad_signatures()`, and BatchNorm in
-batch-statistics mode with ReLU (forward and backward) a ninth, include/catgrasp_amd_bn.h, described by `bn_signatures()`.  `lib()`
-binds and requires all nine.
+batch-statistics mode with ReLU (forward and backward) a ninth, include/catgrasp_amd_bn.h, described by `bn_signatures()`, and the
+screened form of the fused per-point pass a tenth, include/catgrasp_amd_screen.h, described by `screen_signatures()`.  `lib()`
+binds and requires all ten.
 """
 import ctypes
 import os
@@ -38,6 +39,7 @@ NEIGHBORS_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_neighb
 KDTREE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_kdtree.h')   # the k-d tree searches on the grid index: likewise
 SPARSE_GRAD_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_sparse_grad.h')   # the sparse layers' gradients: likewise
 BN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_bn.h')   # batch-statistics BatchNorm + ReLU: likewise
+SCREEN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_screen.h')   # the screened per-point pass: likewise
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -131,6 +133,12 @@ def bn_signatures():
         return signatures(f.read())
 
 
+def screen_signatures():
+    """signatures() of include/catgrasp_amd_screen.h: same parser, same type mapping."""
+    with open(SCREEN_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -140,7 +148,7 @@ def lib():
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
         sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures(),
-                **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures()}
+                **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures(), **screen_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')

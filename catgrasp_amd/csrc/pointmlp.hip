@@ -14,8 +14,9 @@
 // (B operand, pre-packed weight fragments streamed from L2 with global_load_dwordx4), so the
 // max over points is a per-lane reduction over the 16 accumulator registers + one lane^32 swap.
 #include <stdlib.h>
-#include "cg_common.hpp"
+#include "cg_split.hpp"
 #include "../../include/catgrasp_amd.h"
+#include "../../include/catgrasp_amd_screen.h"
 #include "l3_f32_asm.inc"
 
 namespace {
@@ -38,11 +39,43 @@ struct Args {
   int n_main; int tail_split;       // samples [n_main, B) use tail_split workgroups each (tail balancing, see the launcher)
   float* out;                       // (B,1024); pre-filled with -inf when nsplit>1
   float* pointfeat;                 // optional (B,N,64): output of the mid layer (MID==2 only)
+  // SCR only (cg_pointmlp_max_screened): the bf16 hi / lo image of w3 (folding.pack_b_split), an upper bound of every row norm of w3
+  // (+ their maximum at [1024]), the optional counters and the path selector (0 normal, 1 exact stream only, 2 screen first tiles too)
+  const unsigned short* w3s; const float* wn; long long* stats; int force;
 };
 
 // LDS layout (floats): [h2 / hA region: TP*S128] [hB: TP*S64] [xs: TP*XS] [rmax: 1024]
 constexpr int WM_FLOATS = 2 * 8 * 64 * 4;          // the 64 -> 64 layer's B fragments [nb 2][ks 8][lane 64][4]: 16 KB
 constexpr int LDS_FLOATS = TP * S128 + TP * S64 + TP * XS + 1024 + WM_FLOATS;
+
+// ---- the screened 128 -> 1024 layer (SCR; derivation of the bound: DESIGN.md §4.1c) ----
+// Behind the front layers' LDS: [hn: TP floats][ctl: 4 ints][list: SCR_CAP x 16 bit][zt: SCR_CAP floats, only with stats]
+constexpr int SCR_CAP = 3072;                         // (row << 10 | channel) entries a tile may hand to the exact verification
+constexpr int SCR_LDS_BYTES = LDS_FLOATS * 4 + TP * 4 + 16 + SCR_CAP * 2;       // 80,144 B: two workgroups per CU as before
+constexpr int SCR_LDS_BYTES_STATS = SCR_LDS_BYTES + SCR_CAP * 4;
+// E_pc = SCR_KAPPA * wn_c * hn_p + SCR_FLOOR >= |screen value - fmaf chain value| while every wn_c, hn_p <= SCR_RANGE
+constexpr float SCR_KAPPA = 7.f / 65536.f;            // 7 * 2^-16 = 1.068e-4 >= 1.05 * (3.03 * 2^-16 + 1.016 * 384 * 2^-23 + 128 * 2^-24)
+constexpr float SCR_FLOOR = 0x1p-60f;                 // absolute part: pieces / products / sums that underflow
+constexpr float SCR_RANGE = 0x1p30f;
+constexpr float SCR_HN_UP = 1.f + 0x1p-16f;           // rounding of the f32 sum of squares and of the root
+constexpr float SCR_HN_ABS = 0x1p-59f;                // squares below 2^-126 that the sum may have lost
+enum { ST_SCREENED = 0, ST_OVERFLOW = 1, ST_RANGE = 2, ST_FIRST = 3, ST_PAIRS = 4, ST_RATIO = 5, ST_FORCED = 6 };
+
+// max into an LDS float by sign bit, the total order v_max_f32 applies (-0 < +0): see atomic_max_f32
+__device__ __forceinline__ void lds_max_f32(float* addr, float v) {
+  if (!(__float_as_uint(v) >> 31)) atomicMax((int*)addr, __float_as_int(v));
+  else atomicMin((unsigned int*)addr, __float_as_uint(v));
+}
+
+// 8 consecutive floats -> the 16-deep bf16 fragment pieces (hi, lo) of a 32x32x16 operand
+__device__ __forceinline__ void scr_split8(f32x4 v0, f32x4 v1, frag& h, frag& l) {
+  float unused = 0.f;
+  unsigned hh[4], ll[4];
+  split2<false>(v0[0], v0[1], hh[0], ll[0], unused); split2<false>(v0[2], v0[3], hh[1], ll[1], unused);
+  split2<false>(v1[0], v1[1], hh[2], ll[2], unused); split2<false>(v1[2], v1[3], hh[3], ll[3], unused);
+  h = frag{hh[0], hh[1], hh[2], hh[3]};
+  l = frag{ll[0], ll[1], ll[2], ll[3]};
+}
 
 // CS: workgroups that share one (sample, tile slice) and divide the 1024 output channels of the 128 -> 1024 layer between them (each
 // repeats the cheap front layers).  CS = 1 is the throughput kernel; CS = 2 / 4 / 8 serve calls of a few poses (predicter.py:67-94 scores
@@ -50,8 +83,15 @@ constexpr int LDS_FLOATS = TP * S128 + TP * S64 + TP * XS + 1024 + WM_FLOATS;
 // weight image through one MFMA chain per wave (38 us per pass) -- split 8 ways it is 256 workgroups with one 32-channel block per wave.
 // Per output element the sequence of MFMAs is the one the CS = 1 stream issues (k ascending from a zero accumulator), so a
 // candidate's bits do not depend on how many candidates it was scored with.
-template <int MID, int CS>
-__global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
+//
+// SCR (CS == 1 only): the 128 -> 1024 layer of a tile is first SCREENED on bf16 MFMAs (three products per 16 channels, the bf16x3
+// scheme), every (point, channel) pair whose screen value can still reach the channel's maximum is listed, and only the listed pairs
+// are recomputed with the fmaf chain the f32 MFMA stream is defined to equal -- the running maxima, and so every output bit, are those
+// of the exact stream.  A tile whose list overflows, whose activations leave the bound's range, or that is the workgroup's first
+// (rmax still -inf) runs the exact stream instead; that decision is workgroup-uniform and precedes every rmax update of the tile.
+template <int MID, int CS, bool SCR>
+__device__ __forceinline__ void pointmlp_max_body(Args a) {
+  static_assert(!SCR || CS == 1, "the screen serves the throughput path only");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* h2 = smem;                 // also hosts hA (first TP*S64 floats) while h2 is not live
   float* hA = smem;
@@ -59,10 +99,14 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
   float* xs = hB + TP * S64;
   float* rmax = xs + TP * XS;
   f32x4* wms = (f32x4*)(rmax + 1024);      // MID != 0: tile-invariant mid-layer weight fragments, staged once per workgroup
+  float* hn = smem + LDS_FLOATS;           // SCR: upper bounds of the tile's ||h2 row||
+  int* ctl = (int*)(hn + TP);              // SCR: [0] list length, [1] the tile left the bound's range, [2] worst error / bound (stats)
+  unsigned short* list = (unsigned short*)(ctl + 4);
+  float* zt = (float*)(list + SCR_CAP);    // SCR with stats: the listed pairs' screen values
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int w = tid >> 6;
+  const int w = SCR ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;      // SCR: wave-uniform values in scalar registers
   int b, split, nsp;
   const int bid = CS == 1 ? (int)blockIdx.x : (int)blockIdx.x / CS;
   const int cs = CS == 1 ? 0 : (int)blockIdx.x % CS;           // this workgroup's share of the last layer's channels
@@ -80,7 +124,7 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
 
   // per-thread first-layer weights: channel = tid&63
   float w1r[6], b1r;
-  {
+  if constexpr (!SCR) {
     const int ch = tid & 63;
 #pragma unroll
     for (int j = 0; j < 6; ++j) w1r[j] = a.w1[ch * 6 + j];
@@ -89,17 +133,22 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
   float t3r[9];
   if (a.t3) {
 #pragma unroll
-    for (int j = 0; j < 9; ++j) t3r[j] = a.t3[b * 9 + j];
+    for (int j = 0; j < 9; ++j) {
+      t3r[j] = a.t3[b * 9 + j];
+      if constexpr (SCR) t3r[j] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(t3r[j])));      // scalar registers
+    }
   }
   const float* xb = a.x + (size_t)b * a.N * 6;
-  const int l31 = lane & 31;
-  const int lhi = lane >> 5;
   // Tile-invariant operands of the front layers, fetched ONCE per workgroup instead of once per tile with their L2 latency exposed
   // between two barriers: the 64 -> 128 weight fragments of this wave's channel block live in registers, the 64 -> 64 fragments
   // (shared weights, or this sample's feature transform) in LDS.
+  // (SCR: the screen needs the registers -- these operands are re-read from L2 at the head of every tile instead, behind an offset
+  // the compiler cannot see through, or it would hoist the loads and spill their results)
   f32x4 w2r[8];
+  if constexpr (!SCR) {
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) w2r[ks] = ((const f32x4*)a.w2)[(w * 8 + ks) * 64 + lane];
+    for (int ks = 0; ks < 8; ++ks) w2r[ks] = ((const f32x4*)a.w2)[(w * 8 + ks) * 64 + lane];
+  }
   if (MID == 1) {
     for (int i = tid; i < 2 * 8 * 64; i += 256) wms[i] = ((const f32x4*)a.wm)[i];
   }
@@ -119,11 +168,34 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
       xn0 = src[0]; xn1 = src[1]; xn2 = src[2];
     }
   };
-  fetch_points(t_begin);
+  if constexpr (!SCR) fetch_points(t_begin);
+  bool w_ok = true;
+  if (SCR && tid == 0) ctl[2] = 0;        // with stats: bits of the worst |screen - exact| / bound this workgroup has seen
+  if constexpr (SCR) w_ok = a.force != 1 && __float_as_uint(a.wn[1024]) <= __float_as_uint(SCR_RANGE);      // bit compare: NaN / inf / negative fail
 
   for (int tile = t_begin; tile < t_end; ++tile) {
+    // SCR: every lane-dependent index and LDS address of the tile body is re-derived from an opaque copy of the thread id; hoisted out of
+    // the tile loop (the exact kernels have the registers for that) they would be spilled to scratch beside the screen
+    const int tid_outer = tid, lane_outer = lane;
+    int opaque0 = 0;
+    if constexpr (SCR) asm volatile("" : "+v"(opaque0));
+    const int tid = tid_outer + opaque0, lane = lane_outer + opaque0, l31 = lane & 31, lhi = lane >> 5;
     __syncthreads();   // previous tile's L3 reads of h2 / our rmax init are complete
+    if (SCR && tid == 0) { ctl[0] = opaque0; ctl[1] = opaque0; }      // (zero)
+    if constexpr (SCR) {
+      int opaque = 0;
+      asm volatile("" : "+v"(opaque));
+      const int ch = (tid & 63) + opaque;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) w1r[j] = a.w1[ch * 6 + j];
+      b1r = a.b1[ch];
+      if (MID == 0) {
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) w2r[ks] = ((const f32x4*)a.w2)[(w * 8 + ks) * 64 + lane + opaque];
+      }
+    }
     // ---- stage input points (apply the 3x3 input transform to xyz, leave normals) ----
+    if constexpr (SCR) fetch_points(tile);     // no registers to carry them across the screen: read here, the partner workgroup covers the latency
     if (tid < TP) {
       const f32x2 v0 = xn0, v1 = xn1, v2 = xn2;
       float px = v0[0], py = v0[1], pz = v1[0];
@@ -138,7 +210,7 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
       *(f32x4*)(xs + tid * XS) = o0;
       *(f32x4*)(xs + tid * XS + 4) = o1;
     }
-    fetch_points(tile + 1);
+    if constexpr (!SCR) fetch_points(tile + 1);
     __syncthreads();
     // ---- L0: 6 -> 64 on VALU.  thread = (channel, 16-point group) ----
     {
@@ -167,6 +239,12 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
         const f32x4 bv = wms[(nb * 8 + ks) * 64 + lane];
 #pragma unroll
         for (int j = 0; j < 4; ++j) c = mfma32(av[j], bv[j], c);
+      }
+      if constexpr (SCR) {               // requested behind the mid layer's products, used behind its epilogue and a barrier
+        int opaque = 0;
+        asm volatile("" : "+v"(opaque));
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) w2r[ks] = ((const f32x4*)a.w2)[(w * 8 + ks) * 64 + lane + opaque];
       }
       const int col = nb * 32 + l31;
       const float bias = (MID == 1) ? a.bm[col] : 0.f;
@@ -212,6 +290,170 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
     // ---- L3: 128 -> 1024 + running max over points.  wave w owns channel blocks [8w, 8w+8), two at a time x both row tiles.
     // The 1024-MFMA stream of the tile is hand-scheduled assembly (gen_l3_f32_asm.py -> l3_f32_asm.inc): operands prefetched one
     // whole k-step ahead into a double buffer in accumulation registers; it returns the per-lane maxima of the 8 blocks.
+    bool exact = true;
+    if constexpr (SCR) {
+      // upper bound of every row's norm; thread = (row, quarter of the 128 channels)
+      {
+        const int row = tid >> 2, part = tid & 3;
+        const float* hr = h2 + row * S128 + part * 32;
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const f32x4 v = *(const f32x4*)(hr + i * 4);
+          s = fmaf(v[0], v[0], s); s = fmaf(v[1], v[1], s); s = fmaf(v[2], v[2], s); s = fmaf(v[3], v[3], s);
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        const float n = fmaf(sqrtf(s), SCR_HN_UP, SCR_HN_ABS);
+        if (part == 0) {
+          hn[row] = n;
+          if ((__float_as_uint(n) & 0x7fffffffu) > __float_as_uint(SCR_RANGE)) atomicOr(&ctl[1], 1);      // also inf and NaN
+        }
+      }
+      __syncthreads();
+      // tile-invariant addresses and operands of the screen are re-derived per tile behind an offset the compiler cannot see through:
+      // hoisted out of the tile loop they would be spilled
+      int opq = 0;
+      asm volatile("" : "+s"(opq));
+      const unsigned short* w3s_t = a.w3s + opq;
+      const float* wn_t = a.wn + opq;
+      const float* w3_t = a.w3 + opq;
+      const bool first = tile == t_begin && a.force != 2;
+      const bool in_range = w_ok && ctl[1] == 0;
+      exact = first || !in_range;
+      if (!exact) {
+        // ---- screen + select, three (then three, then two) of the wave's eight channel blocks at a time: their 3 x 2 accumulators are
+        // the 96 accumulation registers the exact stream uses, the A fragments (both row tiles, hi / lo) are split from the f32 image
+        // per 16-channel step ----
+        const float* ap = h2 + l31 * S128 + lhi * 8;
+        const float* hq = hn + lhi * 4;
+#pragma unroll 1
+        for (int g = 0; g < 3; ++g) {
+          const int nb0 = w * 8 + g * 3;
+          const int nblk = g < 2 ? 3 : 2;
+          const frag* bp = (const frag*)w3s_t + (size_t)nb0 * (8 * 2 * 64) + lane;         // [nb][kc][hi | lo][lane]
+          f32x16 c[3][2];
+#pragma unroll
+          for (int p = 0; p < 3; ++p) { c[p][0] = f32x16{0}; c[p][1] = f32x16{0}; }
+          // weight fragments [p][hi | lo]: a block's pair for the next 16-channel step is requested into the same registers as soon as
+          // its six products of this step are issued, i.e. two blocks' products (12 MFMAs) ahead of its use
+          frag bq[6];
+#pragma unroll
+          for (int i = 0; i < 6; ++i) if ((i >> 1) < nblk) bq[i] = bp[((i >> 1) * 16 + (i & 1)) * 64];
+#pragma unroll
+          for (int kc = 0; kc < 8; ++kc) {
+            frag ah0, al0, ah1, al1;
+            scr_split8(*(const f32x4*)(ap + kc * 16), *(const f32x4*)(ap + kc * 16 + 4), ah0, al0);
+            scr_split8(*(const f32x4*)(ap + 32 * S128 + kc * 16), *(const f32x4*)(ap + 32 * S128 + kc * 16 + 4), ah1, al1);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+              if (p >= nblk) break;
+              const frag bh = bq[p * 2], bl = bq[p * 2 + 1];
+              c[p][0] = mfma_x<false>(ah0, bl, c[p][0]); c[p][1] = mfma_x<false>(ah1, bl, c[p][1]);
+              c[p][0] = mfma_x<false>(al0, bh, c[p][0]); c[p][1] = mfma_x<false>(al1, bh, c[p][1]);
+              c[p][0] = mfma_x<false>(ah0, bh, c[p][0]); c[p][1] = mfma_x<false>(ah1, bh, c[p][1]);
+              if (kc < 7) {
+                bq[p * 2] = bp[(p * 16 + (kc + 1) * 2) * 64];
+                bq[p * 2 + 1] = bp[(p * 16 + (kc + 1) * 2 + 1) * 64];
+              }
+              __builtin_amdgcn_sched_barrier(0);     // keep the requests here: the scheduler would sink them to their use
+            }
+          }
+          // ---- select: lane = channel, registers = 32 points.  T = max(exact running max, the tile's own lower bound) ----
+#pragma unroll
+          for (int p = 0; p < 3; ++p) {
+            if (p >= nblk) break;
+            __builtin_amdgcn_sched_barrier(0);       // one block's select at a time: interleaved they need the registers of all three
+            const f32x16 c0 = c[p][0], c1 = c[p][1];
+            const int ch = (nb0 + p) * 32 + l31;
+            // E = kw * hn + SCR_FLOOR.  Pass 1: lb = max(c - kw * hn) - SCR_FLOOR; pass 2: list c + kw * hn >= T - SCR_FLOOR.  Two elements
+            // per packed fma; the compare's bit is shifted into the lane's mask through the carry (m = 2 m + bit), top register first.
+            const float kw = SCR_KAPPA * wn_t[ch];
+            const f32x2 pkw = {kw, kw}, nkw = {-kw, -kw};
+            float lb = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const f32x4 n0 = *(const f32x4*)(hq + q * 8), n1 = *(const f32x4*)(hq + 32 + q * 8);
+#pragma unroll
+              for (int j = 0; j < 4; j += 2) {
+                const f32x2 t0 = __builtin_elementwise_fma(nkw, f32x2{n0[j], n0[j + 1]}, f32x2{c0[q * 4 + j], c0[q * 4 + j + 1]});
+                const f32x2 t1 = __builtin_elementwise_fma(nkw, f32x2{n1[j], n1[j + 1]}, f32x2{c1[q * 4 + j], c1[q * 4 + j + 1]});
+                lb = fmaxf(fmaxf(lb, t0[0]), t0[1]);
+                lb = fmaxf(fmaxf(lb, t1[0]), t1[1]);
+              }
+            }
+            lb = fmaxf(lb - SCR_FLOOR, rmax[ch]);
+            const float T = fmaxf(lb, __shfl_xor(lb, 32)) - SCR_FLOOR;
+            unsigned m0 = 0, m1 = 0;
+#pragma unroll
+            for (int q = 3; q >= 0; --q) {
+              const f32x4 n0 = *(const f32x4*)(hq + q * 8), n1 = *(const f32x4*)(hq + 32 + q * 8);
+#pragma unroll
+              for (int j = 2; j >= 0; j -= 2) {
+                const f32x2 u0 = __builtin_elementwise_fma(pkw, f32x2{n0[j], n0[j + 1]}, f32x2{c0[q * 4 + j], c0[q * 4 + j + 1]});
+                const f32x2 u1 = __builtin_elementwise_fma(pkw, f32x2{n1[j], n1[j + 1]}, f32x2{c1[q * 4 + j], c1[q * 4 + j + 1]});
+                asm("v_cmp_ge_f32 vcc, %1, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+                    "v_cmp_ge_f32 vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m0) : "v"(u0[1]), "v"(u0[0]), "v"(T) : "vcc");
+                asm("v_cmp_ge_f32 vcc, %1, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+                    "v_cmp_ge_f32 vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m1) : "v"(u1[1]), "v"(u1[0]), "v"(T) : "vcc");
+              }
+            }
+            const int cnt = __popc(m0) + __popc(m1);
+            if (cnt) {
+              const int at0 = atomicAdd(&ctl[0], cnt);
+              int at = at0;
+              unsigned m = m0;
+#pragma unroll 1
+              for (int rt = 0; rt < 2; ++rt, m = m1) {
+                while (m) {
+                  const int r = __ffs(m) - 1;
+                  m &= m - 1;
+                  if (at < SCR_CAP) list[at] = (unsigned short)(((rt * 32 + acc_row(r, lane)) << 10) | ch);
+                  ++at;
+                }
+              }
+              if (a.stats) {               // the same slots, by static register index
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                  const int i0 = at0 + __popc(m0 & ((1u << r) - 1)), i1 = at0 + __popc(m0) + __popc(m1 & ((1u << r) - 1));
+                  if (((m0 >> r) & 1) && i0 < SCR_CAP) zt[i0] = c0[r];
+                  if (((m1 >> r) & 1) && i1 < SCR_CAP) zt[i1] = c1[r];
+                }
+              }
+            }
+          }
+        }
+        __syncthreads();
+        const int n = ctl[0];
+        if (n > SCR_CAP) {
+          exact = true;                    // nothing of this tile has touched rmax yet
+          if (a.stats && tid == 0) atomicAdd((unsigned long long*)a.stats + ST_OVERFLOW, 1ull);
+        } else {
+          // ---- verify: one listed pair per thread, the operation sequence of the f32 MFMA stream (k-step order, zero accumulator) ----
+          for (int i = tid; i < n; i += 256) {
+            const int e = list[i], row = e >> 10, ch = e & 1023;
+            const float* hr = h2 + row * S128;
+            const f32x4* wp = (const f32x4*)w3_t + (size_t)(ch >> 5) * (16 * 64) + (ch & 31);
+            float z = 0.f;
+#pragma unroll 4
+            for (int ks = 0; ks < 16; ++ks) {
+              const f32x4 w0 = wp[ks * 64], w1 = wp[ks * 64 + 32];
+              const f32x4 h0 = *(const f32x4*)(hr + ks * 8), h1 = *(const f32x4*)(hr + ks * 8 + 4);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) { z = fmaf(h0[j], w0[j], z); z = fmaf(h1[j], w1[j], z); }
+            }
+            lds_max_f32(rmax + ch, z);
+            if (a.stats) atomicMax((unsigned*)&ctl[2], __float_as_uint(fabsf(zt[i] - z) / fmaf(SCR_KAPPA * wn_t[ch], hn[row], SCR_FLOOR)));
+          }
+          if (a.stats && tid == 0) {
+            atomicAdd((unsigned long long*)a.stats + ST_SCREENED, 1ull);
+            atomicAdd((unsigned long long*)a.stats + ST_PAIRS, (unsigned long long)n);
+          }
+        }
+      } else if (a.stats && tid == 0) {
+        atomicAdd((unsigned long long*)a.stats + (a.force == 1 ? ST_FORCED : first ? ST_FIRST : ST_RANGE), 1ull);
+      }
+    }
     if constexpr (CS > 1) {
       constexpr int NBW = 8 / CS;                          // 32-channel blocks per wave
       const float* ar0 = h2 + l31 * S128 + lhi * 4;
@@ -234,7 +476,7 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
         m = fmaxf(m, __shfl_xor(m, 32));
         if (lane < 32) rmax[nb * 32 + lane] = fmaxf(rmax[nb * 32 + lane], m);
       }
-    } else {
+    } else if (exact) {
       const unsigned ar = (unsigned)(uintptr_t)(h2 + l31 * S128 + lhi * 4);      // generic -> LDS byte address = low 32 bits
       const unsigned voff = (unsigned)((w * 8 * 16) * 64 + lane) * 16u;          // this wave's first weight fragment
       float m00, m01, m10, m11, m20, m21, m30, m31, t0, t1;
@@ -259,8 +501,11 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
     }
   }
   __syncthreads();
+  if (SCR && a.stats && tid == 0) atomicMax((unsigned long long*)a.stats + ST_RATIO, (unsigned long long)(unsigned)ctl[2]);      // non-negative floats order as their bits
   if (t_end > t_begin) {
-    for (int ch = tid; ch < 1024; ch += 256) {
+    int tid_e = tid;
+    if constexpr (SCR) asm volatile("" : "+v"(tid_e));      // (the address of rmax[tid] from the prologue would be carried through the tile loop)
+    for (int ch = tid_e; ch < 1024; ch += 256) {
       if (CS > 1 && ch / (1024 / CS) != cs) continue;
       float v = rmax[ch] + a.b3[ch];
       if (a.relu3) v = fmaxf(v, 0.f);
@@ -269,6 +514,18 @@ __global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) {
     }
   }
 }
+
+template <int MID, int CS, bool SCR = false>
+__global__ __launch_bounds__(256) void pointmlp_max_kernel(Args a) { pointmlp_max_body<MID, CS, SCR>(a); }
+// The screened kernels are held to two waves per SIMD (two workgroups per CU, as the exact kernels reach by themselves).
+#define CG_SCREENED_KERNEL(MID)                                                                                          \
+  template <> __global__ __launch_bounds__(256, 2) void pointmlp_max_kernel<MID, 1, true>(Args a) {                     \
+    pointmlp_max_body<MID, 1, true>(a);                                                                                  \
+  }
+CG_SCREENED_KERNEL(0)
+CG_SCREENED_KERNEL(1)
+CG_SCREENED_KERNEL(2)
+#undef CG_SCREENED_KERNEL
 
 __global__ void fill_kernel(float* p, size_t n, float v) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,10 +552,14 @@ CgPointMlpPlan cg_pointmlp_plan(int B, int ntiles, int nsplit, int slots_per_cu,
   return p;
 }
 
-extern "C" int cg_pointmlp_max(const float* x, int B, int N, const float* t3, const float* w1, const float* b1,
-                               int mid_mode, const float* wm_packed, const float* bm, const float* t64,
-                               const float* w2_packed, const float* b2, const float* w3_packed, const float* b3,
-                               int relu3, int nsplit, float* out, float* pointfeat, void* stream) {
+namespace {
+
+// cg_pointmlp_max (w3s == nullptr) and cg_pointmlp_max_screened: one launcher.  The screen serves the throughput kernel (CS == 1);
+// calls of a few poses take the channel-split exact kernels either way.
+int pointmlp_launch(const float* x, int B, int N, const float* t3, const float* w1, const float* b1, int mid_mode, const float* wm_packed,
+                    const float* bm, const float* t64, const float* w2_packed, const float* b2, const float* w3_packed, const float* b3,
+                    int relu3, int nsplit, float* out, float* pointfeat, const unsigned short* w3s, const float* wn, long long* stats,
+                    int force, void* stream) {
   if (!x || !w1 || !b1 || !w2_packed || !b2 || !w3_packed || !b3 || !out) return CG_ERR_ARG;
   if (B < 0 || N <= 0 || mid_mode < 0 || mid_mode > 2) return CG_ERR_ARG;
   if (mid_mode == 1 && (!wm_packed || !bm)) return CG_ERR_ARG;
@@ -306,28 +567,54 @@ extern "C" int cg_pointmlp_max(const float* x, int B, int N, const float* t3, co
   if (pointfeat && mid_mode != 2) return CG_ERR_ARG;
   if (B == 0) return CG_OK;
   hipStream_t s = (hipStream_t)stream;
-  // two resident workgroups per CU (73,728 B of LDS each); the tail is balanced from 8 tiles on, split 8 ways
+  // two resident workgroups per CU (73,728 B of LDS each; 80,144 B screened); the tail is balanced from 8 tiles on, split 8 ways
   const CgPointMlpPlan plan = cg_pointmlp_plan(B, (N + TP - 1) / TP, nsplit, 2, 8, 8, out, s);
   if (plan.status != CG_OK) return plan.status;
   nsplit = plan.nsplit;
   const int n_main = plan.n_main, tail_split = plan.tail_split;
-  Args a{x, B, N, t3, w1, b1, wm_packed, bm, t64, w2_packed, b2, w3_packed, b3, relu3, nsplit, n_main, tail_split, out, pointfeat};
-  const size_t lds = LDS_FLOATS * sizeof(float);          // 73,728 B: above the 64 KB default limit -> per-device function attribute
+  Args a{x, B, N, t3, w1, b1, wm_packed, bm, t64, w2_packed, b2, w3_packed, b3, relu3, nsplit, n_main, tail_split, out, pointfeat,
+         w3s, wn, stats, force};
   // few workgroups (a call of a few poses): divide the last layer's channels over 2 / 4 / 8 workgroups per (sample, slice)
   const long wgs = (long)n_main * nsplit + (long)(B - n_main) * tail_split;
   int csi = tail_split > 1 ? 0 : wgs <= 64 ? 3 : wgs <= 128 ? 2 : wgs <= 256 ? 1 : 0;
   static const char* cs_env = getenv("CATGRASP_AMD_POINTMLP_CSPLIT");     // dev knob: 1 / 2 / 4 / 8
   if (cs_env) { const int v = atoi(cs_env); csi = tail_split > 1 ? 0 : v == 8 ? 3 : v == 4 ? 2 : v == 2 ? 1 : 0; }
-  static bool lds_allowed[3][4][CG_MAX_DEVICES] = {};
+  if (w3s && csi == 0) csi = 4;           // the screened throughput kernel
+  static bool lds_allowed[3][5][CG_MAX_DEVICES] = {};
   typedef void (*kern_t)(Args);
-  static const kern_t kerns[3][4] = {
-      {pointmlp_max_kernel<0, 1>, pointmlp_max_kernel<0, 2>, pointmlp_max_kernel<0, 4>, pointmlp_max_kernel<0, 8>},
-      {pointmlp_max_kernel<1, 1>, pointmlp_max_kernel<1, 2>, pointmlp_max_kernel<1, 4>, pointmlp_max_kernel<1, 8>},
-      {pointmlp_max_kernel<2, 1>, pointmlp_max_kernel<2, 2>, pointmlp_max_kernel<2, 4>, pointmlp_max_kernel<2, 8>}};
+  static const kern_t kerns[3][5] = {
+      {pointmlp_max_kernel<0, 1>, pointmlp_max_kernel<0, 2>, pointmlp_max_kernel<0, 4>, pointmlp_max_kernel<0, 8>, pointmlp_max_kernel<0, 1, true>},
+      {pointmlp_max_kernel<1, 1>, pointmlp_max_kernel<1, 2>, pointmlp_max_kernel<1, 4>, pointmlp_max_kernel<1, 8>, pointmlp_max_kernel<1, 1, true>},
+      {pointmlp_max_kernel<2, 1>, pointmlp_max_kernel<2, 2>, pointmlp_max_kernel<2, 4>, pointmlp_max_kernel<2, 8>, pointmlp_max_kernel<2, 1, true>}};
   const kern_t kern = kerns[mid_mode][csi];
-  const int st = cg_allow_dynamic_lds((const void*)kern, plan.dev, lds, lds_allowed[mid_mode][csi]);
+  // 73,728 B and up: above the 64 KB default limit -> per-device function attribute (the screened kernel's larger size with counters
+  // has a flag row of its own: the attribute is set to the largest size a row has asked for)
+  const bool scr = csi == 4;
+  const size_t lds = !scr ? LDS_FLOATS * sizeof(float) : stats ? SCR_LDS_BYTES_STATS : SCR_LDS_BYTES;
+  const int st = cg_allow_dynamic_lds((const void*)kern, plan.dev, scr ? (size_t)SCR_LDS_BYTES_STATS : lds, lds_allowed[mid_mode][csi]);
   if (st != CG_OK) return st;
-  dim3 grid((unsigned)(wgs << csi)), block(256);
+  dim3 grid((unsigned)(wgs << (scr ? 0 : csi))), block(256);
   hipLaunchKernelGGL(kern, grid, block, lds, s, a);
   return cg_hip_status(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int cg_pointmlp_max(const float* x, int B, int N, const float* t3, const float* w1, const float* b1,
+                               int mid_mode, const float* wm_packed, const float* bm, const float* t64,
+                               const float* w2_packed, const float* b2, const float* w3_packed, const float* b3,
+                               int relu3, int nsplit, float* out, float* pointfeat, void* stream) {
+  return pointmlp_launch(x, B, N, t3, w1, b1, mid_mode, wm_packed, bm, t64, w2_packed, b2, w3_packed, b3, relu3, nsplit, out, pointfeat,
+                         nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int cg_pointmlp_max_screened(const float* x, int B, int N, const float* t3, const float* w1, const float* b1,
+                                        int mid_mode, const float* wm_packed, const float* bm, const float* t64,
+                                        const float* w2_packed, const float* b2, const float* w3_packed, const float* b3,
+                                        int relu3, int nsplit, float* out, float* pointfeat, const unsigned short* w3_split,
+                                        const float* w3_norm, long long* stats, int force, void* stream) {
+  if (!w3_split || !w3_norm || force < 0 || force > 2) return CG_ERR_ARG;
+  if (((uintptr_t)w3_split & 15) != 0) return CG_ERR_ARG;
+  return pointmlp_launch(x, B, N, t3, w1, b1, mid_mode, wm_packed, bm, t64, w2_packed, b2, w3_packed, b3, relu3, nsplit, out, pointfeat,
+                         w3_split, w3_norm, stats, force, stream);
 }

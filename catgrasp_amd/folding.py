@@ -76,7 +76,33 @@ def pack_b_split(w, elem='bf16'):
     return np.ascontiguousarray(out).reshape(-1)
 
 
-MX_NB_BYTES = 16640        # csrc/gen_l3_mx_asm.py: f16 fragments 8192 | lo8 4096 | hi8 4096 | scales 256
+SCREEN_NORM_MAX = 2.0 ** 30        # csrc/pointmlp.hip: SCR_RANGE, the largest row norm the screen's error bound is derived for
+# the bound itself, as csrc/pointmlp.hip states it: E = KAPPA * wn_c * hn_p + FLOOR, hn_p = ||h_p|| * HN_UP + HN_ABS
+SCREEN_KAPPA, SCREEN_FLOOR, SCREEN_HN_UP, SCREEN_HN_ABS = 7.0 * 2.0 ** -16, 2.0 ** -60, 1.0 + 2.0 ** -16, 2.0 ** -59
+
+
+def screen_norms(w):
+    """W:(1024,K) folded weights of a 128 -> 1024 layer -> float32 (1025,): entry c an UPPER bound of ||W[c]||_2 (float64 norm of
+    the float32 weights, inflated by 2^-40 for the float64 sum and root, then rounded up to float32); entry 1024 the largest of
+    them, which cg_pointmlp_max_screened tests against its range once per workgroup."""
+    w = np.asarray(w, dtype=np.float32).astype(np.float64)
+    n = np.sqrt((w * w).sum(axis=1)) * (1.0 + 2.0 ** -40)
+    f = n.astype(np.float32)
+    f = np.where(f.astype(np.float64) < n, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+    return np.concatenate([f, f.max(keepdims=True)]).astype(np.float32)
+
+
+def attach_screen(w3_packed, w3_split, w):
+    """Hang the screen's operands on the packed f32 image of a 128 -> 1024 layer: `w3_packed.screen = (bf16 split image, norms)`,
+    which ops.pointmlp_max turns into a cg_pointmlp_max_screened call.  A layer outside the screen's range (non-finite or huge
+    rows) gets none and runs the exact entry."""
+    norms = screen_norms(w)
+    if np.isfinite(norms).all() and float(norms[-1]) <= SCREEN_NORM_MAX:
+        w3_packed.screen = (w3_split, torch.from_numpy(norms).to(w3_packed.device))
+    return w3_packed
+
+
+MX_NB_BYTES = 16640       # csrc/gen_l3_mx_asm.py: f16 fragments 8192 | lo8 4096 | hi8 4096 | scales 256
 
 
 def _e4m3_bits(x):
@@ -206,6 +232,7 @@ def _prepare_tnet(W, sd, q, tag, k):
     W.put(tag + '.w2', pack_b(w)); W.put(tag + '.b2', b); W.put_split(tag + '.w2.s', w)
     w, b = fold_bn(*_conv(sd, q + 'conv3'), _bn(sd, q + 'bn3'))
     W.put(tag + '.w3', pack_b(w)); W.put(tag + '.b3', b); W.put_split(tag + '.w3.s', w); W.put_mx(tag + '.w3.q', w)
+    attach_screen(W[tag + '.w3'], W[tag + '.w3.s'], w)
     w, b = fold_bn(_get(sd, q + 'fc1.weight'), _get(sd, q + 'fc1.bias'), _bn(sd, q + 'bn4'))
     W.put(tag + '.fc1', pack_b(w)); W.put(tag + '.fc1b', b); W.put_half(tag + '.fc1.h', w)
     w, b = fold_bn(_get(sd, q + 'fc2.weight'), _get(sd, q + 'fc2.bias'), _bn(sd, q + 'bn5'))
@@ -265,6 +292,7 @@ def prepare_encoder(sd, prefix, device, out=None):
     W.put('enc.w2', pack_b(w)); W.put('enc.b2', b); W.put_split('enc.w2.s', w)
     w, b = fold_bn(*_conv(sd, p + 'conv3'), _bn(sd, p + 'bn3'))
     W.put('enc.w3', pack_b(w)); W.put('enc.b3', b); W.put_split('enc.w3.s', w); W.put_mx('enc.w3.q', w)
+    attach_screen(W['enc.w3'], W['enc.w3.s'], w)
     return W
 
 

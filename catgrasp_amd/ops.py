@@ -19,6 +19,10 @@ _POINTMLP_KERNELS = {False: ('cg_pointmlp_max', False, False), 'bf16': ('cg_poin
                      'f16': ('cg_pointmlp_max_f16x3', True, True), 'f16fp8': ('cg_pointmlp_max_f16fp8x2', True, True)}
 
 
+SCREEN = True           # False: exact-f32 passes take cg_pointmlp_max even where the weights carry the screen's images
+SCREEN_STATS = None     # measurement hook: a zeroed (8,) int64 device tensor collects cg_pointmlp_max_screened's counters
+
+
 def pointmlp_max(x, w1, b1, w2p, b2, w3p, b3, relu3, t3=None, mid_mode=0, wm=None, bm=None, t64=None,
                  nsplit=1, pointfeat=False, split=False, tile_points=256, status=None):
     """x:(B,N,6) -> (B,1024) [, pointfeat (B,N,64)].  See cg_pointmlp_max / cg_pointmlp_max_bf16x3 in
@@ -38,6 +42,10 @@ def pointmlp_max(x, w1, b1, w2p, b2, w3p, b3, relu3, t3=None, mid_mode=0, wm=Non
     if timer is not None:
         ev0 = torch.cuda.Event(enable_timing=True); ev1 = torch.cuda.Event(enable_timing=True)
         ev0.record()
+    screen = None if split else getattr(w3p, 'screen', None)
+    if screen is not None and SCREEN:      # the packed f32 image carries the screen's operands (folding.attach_screen): same bits, less work
+        name = 'cg_pointmlp_max_screened'
+        args = args[:-1] + (_p(screen[0]), _p(screen[1]), _p(SCREEN_STATS), 0, args[-1])
     st = getattr(L.lib(), name)(*args)
     if timer is not None:
         ev1.record()
