@@ -77,6 +77,13 @@ __device__ __forceinline__ void scr_split8(f32x4 v0, f32x4 v1, frag& h, frag& l)
   l = frag{ll[0], ll[1], ll[2], ll[3]};
 }
 
+// the hi pieces alone: the first conversion of split2<false>, one v_cvt_pk_bf16_f32 per two elements
+__device__ __forceinline__ frag scr_hi8(f32x4 v0, f32x4 v1) {
+  const bf16x2 h0 = {(__bf16)v0[0], (__bf16)v0[1]}, h1 = {(__bf16)v0[2], (__bf16)v0[3]};
+  const bf16x2 h2 = {(__bf16)v1[0], (__bf16)v1[1]}, h3 = {(__bf16)v1[2], (__bf16)v1[3]};
+  return frag{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1), __builtin_bit_cast(unsigned, h2), __builtin_bit_cast(unsigned, h3)};
+}
+
 // CS: workgroups that share one (sample, tile slice) and divide the 1024 output channels of the 128 -> 1024 layer between them (each
 // repeats the cheap front layers).  CS = 1 is the throughput kernel; CS = 2 / 4 / 8 serve calls of a few poses (predicter.py:67-94 scores
 // a few hundred per object, a live caller one at a time): one pose is 32 tiles, i.e. 32 workgroups that each stream the whole 0.5 MB
@@ -99,6 +106,12 @@ __device__ __forceinline__ void pointmlp_max_body(Args a) {
   float* xs = hB + TP * S64;
   float* rmax = xs + TP * XS;
   f32x4* wms = (f32x4*)(rmax + 1024);      // MID != 0: tile-invariant mid-layer weight fragments, staged once per workgroup
+  // SCR: the bf16 lo pieces of the h2 tile, [row][128] at hB's own row stride (S64 dwords = 272 B, conflict-free ds_read_b128 for the
+  // same lane pattern as the f32 reads of hB).  It fills hB exactly (TP * S64 dwords) and leaves xs alone.  hB is dead while the image
+  // lives: its last readers (the 64 -> 128 products) precede the barrier that completes h2, the image is written behind that barrier
+  // and last read by the screen, which precedes the next tile's first barrier; hB's next writers (the 6 -> 64 layer for MID == 0, the
+  // mid layer otherwise) follow that barrier.  pointfeat is written from registers, not from hB.
+  unsigned* hlo = (unsigned*)hB;
   float* hn = smem + LDS_FLOATS;           // SCR: upper bounds of the tile's ||h2 row||
   int* ctl = (int*)(hn + TP);              // SCR: [0] list length, [1] the tile left the bound's range, [2] worst error / bound (stats)
   unsigned short* list = (unsigned short*)(ctl + 4);
@@ -292,15 +305,21 @@ __device__ __forceinline__ void pointmlp_max_body(Args a) {
     // whole k-step ahead into a double buffer in accumulation registers; it returns the per-lane maxima of the 8 blocks.
     bool exact = true;
     if constexpr (SCR) {
-      // upper bound of every row's norm; thread = (row, quarter of the 128 channels)
+      // upper bound of every row's norm; thread = (row, quarter of the 128 channels).  The same pass splits the tile ONCE: the bf16 lo
+      // pieces of its 32 elements go to the hlo image (the screen forms the hi pieces from the f32 fragments it reads anyway).
       {
         const int row = tid >> 2, part = tid & 3;
         const float* hr = h2 + row * S128 + part * 32;
+        frag* lr = (frag*)(hlo + row * S64 + part * 16);
         float s = 0.f;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const f32x4 v = *(const f32x4*)(hr + i * 4);
+        for (int i = 0; i < 4; ++i) {
+          const f32x4 v = *(const f32x4*)(hr + i * 8), u = *(const f32x4*)(hr + i * 8 + 4);
           s = fmaf(v[0], v[0], s); s = fmaf(v[1], v[1], s); s = fmaf(v[2], v[2], s); s = fmaf(v[3], v[3], s);
+          s = fmaf(u[0], u[0], s); s = fmaf(u[1], u[1], s); s = fmaf(u[2], u[2], s); s = fmaf(u[3], u[3], s);
+          frag hi_unused, lo;
+          scr_split8(v, u, hi_unused, lo);
+          lr[i] = lo;
         }
         s += __shfl_xor(s, 1);
         s += __shfl_xor(s, 2);
@@ -323,9 +342,10 @@ __device__ __forceinline__ void pointmlp_max_body(Args a) {
       exact = first || !in_range;
       if (!exact) {
         // ---- screen + select, three (then three, then two) of the wave's eight channel blocks at a time: their 3 x 2 accumulators are
-        // the 96 accumulation registers the exact stream uses, the A fragments (both row tiles, hi / lo) are split from the f32 image
-        // per 16-channel step ----
+        // the 96 accumulation registers the exact stream uses, the A fragments (both row tiles) are the bf16 conversion of the f32 image (hi) and
+        // the hlo image (lo), read per 16-channel step ----
         const float* ap = h2 + l31 * S128 + lhi * 8;
+        const frag* lp = (const frag*)(hlo + l31 * S64 + lhi * 4);
         const float* hq = hn + lhi * 4;
 #pragma unroll 1
         for (int g = 0; g < 3; ++g) {
@@ -340,11 +360,19 @@ __device__ __forceinline__ void pointmlp_max_body(Args a) {
           frag bq[6];
 #pragma unroll
           for (int i = 0; i < 6; ++i) if ((i >> 1) < nblk) bq[i] = bp[((i >> 1) * 16 + (i & 1)) * 64];
+          // A operands of a 16-channel step, both row tiles: the f32 fragments (hi = their bf16 conversion) and the lo fragments of the
+          // hlo image, requested behind the previous step's products.  (Requested a whole step earlier they gained 0.1 %: not kept.)
+          f32x4 fa[4];
+          frag fl[2];
+          auto read_a = [&](int kc) {
+            fa[0] = *(const f32x4*)(ap + kc * 16); fa[1] = *(const f32x4*)(ap + kc * 16 + 4);
+            fa[2] = *(const f32x4*)(ap + 32 * S128 + kc * 16); fa[3] = *(const f32x4*)(ap + 32 * S128 + kc * 16 + 4);
+            fl[0] = lp[kc * 2]; fl[1] = lp[32 * (S64 / 4) + kc * 2];
+          };
+          read_a(0);
 #pragma unroll
           for (int kc = 0; kc < 8; ++kc) {
-            frag ah0, al0, ah1, al1;
-            scr_split8(*(const f32x4*)(ap + kc * 16), *(const f32x4*)(ap + kc * 16 + 4), ah0, al0);
-            scr_split8(*(const f32x4*)(ap + 32 * S128 + kc * 16), *(const f32x4*)(ap + 32 * S128 + kc * 16 + 4), ah1, al1);
+            const frag ah0 = scr_hi8(fa[0], fa[1]), ah1 = scr_hi8(fa[2], fa[3]), al0 = fl[0], al1 = fl[1];
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
               if (p >= nblk) break;
@@ -358,6 +386,7 @@ __device__ __forceinline__ void pointmlp_max_body(Args a) {
               }
               __builtin_amdgcn_sched_barrier(0);     // keep the requests here: the scheduler would sink them to their use
             }
+            if (kc < 7) read_a(kc + 1);
           }
           // ---- select: lane = channel, registers = 32 points.  T = max(exact running max, the tile's own lower bound) ----
 #pragma unroll
