@@ -4,6 +4,7 @@ import pytest
 
 from catgrasp_amd import synth
 from oracle import aligning_ref
+from ransac_cases import T_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -43,10 +44,13 @@ def test_hypotheses_and_best_transform_match_oracle(cuda_device):
     ref_c = np.array([-1 if o is None else o[0] for o in outs])
     assert (ref_c >= 0).sum() > 20 and (ref_c < 0).sum() > 20 and ref_c[5] == -1
     assert np.array_equal(c, ref_c), f'{(c != ref_c).sum()} hypotheses disagree'
-    for i in np.flatnonzero(ref_c >= 0)[:50]:
-        assert np.abs(Ts[i] - outs[i][1]).max() < 1e-9
+    # every accepted transform within the measured-and-recorded bound of tests/ransac_cases.py (T_TOL, 16 x the larger of the device's
+    # and the oracle's own float64 error)
+    gap = max(float(np.abs(Ts[i] - outs[i][1]).max()) for i in np.flatnonzero(ref_c >= 0))
+    print(f'MEASURED device vs oracle, largest |dT| over {int((ref_c >= 0).sum())} accepted hypotheses: {gap:.3e}')
+    assert gap <= T_TOL
     T, inl = aligning.estimate9DTransform(src, dst, 0.003, max_iter=len(ids), max_scale=max_s, min_scale=min_s, max_dimensions=max_d, ids=ids)
-    assert np.abs(T - T_ref).max() < 1e-9 and np.array_equal(inl, inl_ref)
+    assert np.abs(T - T_ref).max() <= T_TOL and np.array_equal(inl, inl_ref)
     # and it actually recovers the pose
     assert np.abs(T[:3, 3] - T_true[:3, 3]).max() < 2e-3
     assert np.abs(np.linalg.norm(T[:3, :3], axis=0) - np.array([0.016, 0.02, 0.007])).max() < 2e-3
