@@ -19,8 +19,9 @@ a sixth, include/catgrasp_amd_neighbors.h, described by `neighbors_signatures()`
 nearest neighbour, ball lists) a seventh, include/catgrasp_amd_kdtree.h, described by `kdtree_signatures()`, and the gradients of the
 sparse convolution layers an eighth, include/catgrasp_amd_sparse_grad.h, described by `sparse_grad_signatures()`, and BatchNorm in
 batch-statistics mode with ReLU (forward and backward) a ninth, include/catgrasp_amd_bn.h, described by `bn_signatures()`, and the
-screened form of the fused per-point pass a tenth, include/catgrasp_amd_screen.h, described by `screen_signatures()`.  `lib()`
-binds and requires all ten.
+screened form of the fused per-point pass a tenth, include/catgrasp_amd_screen.h, described by `screen_signatures()`, and the NUNOCS
+training loss (forward and backward) an eleventh, include/catgrasp_amd_loss.h, described by `loss_signatures()`.  `lib()` binds and
+requires all eleven.
 """
 import ctypes
 import os
@@ -40,6 +41,7 @@ KDTREE_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_kdtree.h'
 SPARSE_GRAD_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_sparse_grad.h')   # the sparse layers' gradients: likewise
 BN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_bn.h')   # batch-statistics BatchNorm + ReLU: likewise
 SCREEN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_screen.h')   # the screened per-point pass: likewise
+LOSS_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_loss.h')   # the NUNOCS training loss: likewise
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -139,6 +141,12 @@ def screen_signatures():
         return signatures(f.read())
 
 
+def loss_signatures():
+    """signatures() of include/catgrasp_amd_loss.h: same parser, same type mapping."""
+    with open(LOSS_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -148,7 +156,8 @@ def lib():
                 '(hipcc --offload-arch=gfx950).  There is no CPU fallback.')
         l = ctypes.CDLL(LIB_PATH)
         sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures(),
-                **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures(), **screen_signatures()}
+                **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures(), **screen_signatures(),
+                **loss_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')
