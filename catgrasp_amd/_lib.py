@@ -20,8 +20,10 @@ nearest neighbour, ball lists) a seventh, include/catgrasp_amd_kdtree.h, describ
 sparse convolution layers an eighth, include/catgrasp_amd_sparse_grad.h, described by `sparse_grad_signatures()`, and BatchNorm in
 batch-statistics mode with ReLU (forward and backward) a ninth, include/catgrasp_amd_bn.h, described by `bn_signatures()`, and the
 screened form of the fused per-point pass a tenth, include/catgrasp_amd_screen.h, described by `screen_signatures()`, and the NUNOCS
-training loss (forward and backward) an eleventh, include/catgrasp_amd_loss.h, described by `loss_signatures()`.  `lib()` binds and
-requires all eleven.
+training loss (forward and backward) an eleventh, include/catgrasp_amd_loss.h, described by `loss_signatures()`.  The gradients of the
+dense per-row layers (weight, bias, input, per-group column sums) and BatchNorm + ReLU at the widths of PointNetSeg's head have a
+twelfth, which lives inside the package, catgrasp_amd/include/catgrasp_amd_dense.h, described by `dense_signatures()`.  `lib()` binds
+and requires all twelve.
 """
 import ctypes
 import os
@@ -42,6 +44,7 @@ SPARSE_GRAD_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_spar
 BN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_bn.h')   # batch-statistics BatchNorm + ReLU: likewise
 SCREEN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_screen.h')   # the screened per-point pass: likewise
 LOSS_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_loss.h')   # the NUNOCS training loss: likewise
+DENSE_HEADER_PATH = os.path.join(_PKG, 'include', 'catgrasp_amd_dense.h')   # the dense layers' gradients: likewise, inside the package
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -147,6 +150,12 @@ def loss_signatures():
         return signatures(f.read())
 
 
+def dense_signatures():
+    """signatures() of catgrasp_amd/include/catgrasp_amd_dense.h: same parser, same type mapping."""
+    with open(DENSE_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -157,7 +166,7 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures(),
                 **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures(), **screen_signatures(),
-                **loss_signatures()}
+                **loss_signatures(), **dense_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')

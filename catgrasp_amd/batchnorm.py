@@ -9,8 +9,10 @@ of f32 chains that depends on n alone (the header has it), there are no atomics,
 stream.  The activation is fmaxf(x*scale + shift, 0), the inference kernel's prologue with the batch's constants; the backward
 recomputes the ReLU mask from x, scale and shift, so nothing but x and five (c) vectors is kept (one (5, c) tensor).
 
-c is a multiple of 16 up to 224, 2 <= n <= 2^24, float32, HIP device tensors only; there is no CPU implementation and no double
-backward."""
+c is a multiple of 16 up to 1024, 2 <= n <= 2^24, float32, HIP device tensors only; there is no CPU implementation and no double
+backward.  Widths up to 224 (the sparse networks') run through the entry points of include/catgrasp_amd_bn.h, wider ones (the 512 /
+256 / 128 of PointNetSeg's head) through the `_wide` ones of catgrasp_amd/include/catgrasp_amd_dense.h: the same kernels and the same
+tree, only the limit differs, and at c <= 224 both give the same bits."""
 import ctypes
 
 import torch
@@ -20,34 +22,46 @@ from torch.autograd.function import once_differentiable
 from . import _lib as L
 from ._lib import _p, _stream, check
 
-MAX_C = 224
+MAX_C = 224            # the entry points of catgrasp_amd_bn.h
+WIDE_MAX_C = 1024      # the `_wide` entry points of catgrasp_amd_dense.h
 
 
-def _workspace(n, c, dev):
-    size = int(L.lib().cg_bn_workspace(n, c))
-    check(min(size, 0), 'cg_bn_workspace')
+def _entry(c, wide):
+    """(workspace, forward, backward) symbol names for width c; wide=None: by the width."""
+    if wide or (wide is None and c > MAX_C):
+        return 'cg_bn_wide_workspace', 'cg_bn_relu_train_forward_wide', 'cg_bn_relu_train_backward_wide'
+    return 'cg_bn_workspace', 'cg_bn_relu_train_forward', 'cg_bn_relu_train_backward'
+
+
+def _workspace(n, c, dev, wide=None):
+    name = _entry(c, wide)[0]
+    size = int(getattr(L.lib(), name)(n, c))
+    check(min(size, 0), name)
     return torch.empty((size,), dtype=torch.float32, device=dev)
 
 
-def bn_relu_forward(x, gamma, beta, eps):
-    """-> (y (n, c), stats (5, c): the rows mean, var (biased), invstd, scale, shift) of a contiguous float32 device x."""
+def bn_relu_forward(x, gamma, beta, eps, wide=None):
+    """-> (y (n, c), stats (5, c): the rows mean, var (biased), invstd, scale, shift) of a contiguous float32 device x.
+    wide: True / False forces the `_wide` / the catgrasp_amd_bn.h entry points, None takes them by the width."""
     n, c = x.shape
+    name = _entry(c, wide)[1]
     y = torch.empty_like(x)
     stats = torch.empty((5, c), dtype=torch.float32, device=x.device)
     rows = [ctypes.c_void_p(stats.data_ptr() + 4 * c * i) for i in range(5)]
-    check(L.lib().cg_bn_relu_train_forward(_p(L.f32c(x)), n, c, _p(L.f32c(gamma)), _p(L.f32c(beta)), float(eps), _p(_workspace(n, c, x.device)),
-                                           *rows, _p(y), _stream()), 'cg_bn_relu_train_forward')
+    check(getattr(L.lib(), name)(_p(L.f32c(x)), n, c, _p(L.f32c(gamma)), _p(L.f32c(beta)), float(eps), _p(_workspace(n, c, x.device, wide)),
+                                 *rows, _p(y), _stream()), name)
     return y, stats
 
 
-def bn_relu_backward(x, dy, stats, need_dx=True):
-    """-> (dx (n, c) or None, dgamma (c), dbeta (c)) for dy = dL/dy and the forward's stats."""
+def bn_relu_backward(x, dy, stats, need_dx=True, wide=None):
+    """-> (dx (n, c) or None, dgamma (c), dbeta (c)) for dy = dL/dy and the forward's stats.  wide: as in bn_relu_forward."""
     n, c = x.shape
+    name = _entry(c, wide)[2]
     dx = torch.empty_like(x) if need_dx else None
     dgamma, dbeta = (torch.empty((c,), dtype=torch.float32, device=x.device) for _ in range(2))
     mean, _, invstd, scale, shift = (ctypes.c_void_p(stats.data_ptr() + 4 * c * i) for i in range(5))
-    check(L.lib().cg_bn_relu_train_backward(_p(L.f32c(x)), _p(L.f32c(dy)), n, c, mean, invstd, scale, shift,
-                                            _p(_workspace(n, c, x.device)), _p(dgamma), _p(dbeta), _p(dx), _stream()), 'cg_bn_relu_train_backward')
+    check(getattr(L.lib(), name)(_p(L.f32c(x)), _p(L.f32c(dy)), n, c, mean, invstd, scale, shift,
+                                 _p(_workspace(n, c, x.device, wide)), _p(dgamma), _p(dbeta), _p(dx), _stream()), name)
     return dx, dgamma, dbeta
 
 
@@ -92,8 +106,8 @@ def bn_relu_train(x, bn):
     n, c = x.shape
     if n <= 1:
         raise ValueError(f'Expected more than 1 value per channel when training, got input size {x.size()}')
-    if c % 16 or c > MAX_C:
-        raise NotImplementedError(f'bn_relu_train takes widths that are multiples of 16 up to {MAX_C}, got {c}')
+    if c % 16 or c > WIDE_MAX_C:
+        raise NotImplementedError(f'bn_relu_train takes widths that are multiples of 16 up to {WIDE_MAX_C}, got {c}')
     y, stats = BatchNormReLUFunction.apply(x, bn.weight, bn.bias, bn.eps)
     with torch.no_grad():
         m = bn.momentum

@@ -38,6 +38,7 @@ def build(force=False, verbose=True):
     hdrs += [os.path.join(PKG_DIR, '..', 'include', h) for h in ('catgrasp_amd.h', 'catgrasp_amd_cluster.h', 'catgrasp_amd_sparse.h', 'catgrasp_amd_pointgroup.h',
                                                                  'catgrasp_amd_scene.h', 'catgrasp_amd_neighbors.h', 'catgrasp_amd_kdtree.h', 'catgrasp_amd_sparse_grad.h', 'catgrasp_amd_bn.h',
                                                                  'catgrasp_amd_screen.h', 'catgrasp_amd_loss.h')]
+    hdrs.append(os.path.join(PKG_DIR, 'include', 'catgrasp_amd_dense.h'))      # the dense layers' gradients: a header inside the package
     objs = []
     jobs = []
     for s in srcs:

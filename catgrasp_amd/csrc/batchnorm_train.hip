@@ -16,11 +16,13 @@
 //              bn_dx_kernel           dbeta, dgamma (chunk 0 writes them); dx (one chunk of workgroups and no row work when dx is NULL)
 #include "cg_common.hpp"
 #include "../../include/catgrasp_amd_bn.h"
+#include "../include/catgrasp_amd_dense.h"
 
 namespace {
 
 constexpr int SEG = CG_BN_SEG, ROWS = CG_BN_ROWS, WAVES = ROWS / SEG, LANES = 64;
 constexpr long MAX_N = 1L << 24;
+constexpr int NARROW_C = 224;
 static_assert(WAVES == 16 && SEG == 64, "one wave per segment, 16 waves per workgroup");
 
 enum { SUM_X, SUM_DD, SUM_G };
@@ -161,23 +163,22 @@ __global__ __launch_bounds__(ROWS) void bn_dx_kernel(const float* __restrict__ x
   }
 }
 
-int check_shape(long n, int c) {
+// max_c: 224 for the entry points of catgrasp_amd_bn.h, CG_DENSE_MAX_C for the wide ones of catgrasp_amd_dense.h -- the one difference
+int check_shape(long n, int c, int max_c) {
   if (n < 2 || n > MAX_N || c <= 0) return CG_ERR_ARG;
-  if (c % 16 != 0 || c > 224) return CG_ERR_UNSUPPORTED;
+  if (c % 16 != 0 || c > max_c) return CG_ERR_UNSUPPORTED;
   return CG_OK;
 }
 
-}  // namespace
-
-extern "C" long cg_bn_workspace(long n, int c) {
-  const int st = check_shape(n, c);
+long workspace_size(long n, int c, int max_c) {
+  const int st = check_shape(n, c, max_c);
   if (st != CG_OK) return st;
   return 2L * c * ((n + ROWS - 1) / ROWS);
 }
 
-extern "C" int cg_bn_relu_train_forward(const float* x, long n, int c, const float* gamma, const float* beta, float eps, float* workspace,
-                                        float* mean, float* var, float* invstd, float* scale, float* shift, float* y, void* stream) {
-  const int st = check_shape(n, c);
+int forward(const float* x, long n, int c, const float* gamma, const float* beta, float eps, float* workspace, float* mean, float* var,
+            float* invstd, float* scale, float* shift, float* y, void* stream, int max_c) {
+  const int st = check_shape(n, c, max_c);
   if (st != CG_OK) return st;
   if (!x || !gamma || !beta || !workspace || !mean || !var || !invstd || !scale || !shift || !y) return CG_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -195,10 +196,9 @@ extern "C" int cg_bn_relu_train_forward(const float* x, long n, int c, const flo
   return cg_hip_status(hipGetLastError());
 }
 
-extern "C" int cg_bn_relu_train_backward(const float* x, const float* dy, long n, int c, const float* mean, const float* invstd,
-                                         const float* scale, const float* shift, float* workspace, float* dgamma, float* dbeta, float* dx,
-                                         void* stream) {
-  const int st = check_shape(n, c);
+int backward(const float* x, const float* dy, long n, int c, const float* mean, const float* invstd, const float* scale, const float* shift,
+             float* workspace, float* dgamma, float* dbeta, float* dx, void* stream, int max_c) {
+  const int st = check_shape(n, c, max_c);
   if (st != CG_OK) return st;
   if (!x || !dy || !mean || !invstd || !scale || !shift || !workspace || !dgamma || !dbeta) return CG_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -211,4 +211,33 @@ extern "C" int cg_bn_relu_train_backward(const float* x, const float* dy, long n
   hipLaunchKernelGGL(bn_dx_kernel, dim3(dx ? (unsigned)chunks : 1u, groups), block, 0, s, x, dy, n, c, chunks, mean, invstd, scale, shift,
                      (const float*)workspace, dgamma, dbeta, dx);
   return cg_hip_status(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" long cg_bn_workspace(long n, int c) { return workspace_size(n, c, NARROW_C); }
+
+extern "C" int cg_bn_relu_train_forward(const float* x, long n, int c, const float* gamma, const float* beta, float eps, float* workspace,
+                                        float* mean, float* var, float* invstd, float* scale, float* shift, float* y, void* stream) {
+  return forward(x, n, c, gamma, beta, eps, workspace, mean, var, invstd, scale, shift, y, stream, NARROW_C);
+}
+
+extern "C" int cg_bn_relu_train_backward(const float* x, const float* dy, long n, int c, const float* mean, const float* invstd,
+                                         const float* scale, const float* shift, float* workspace, float* dgamma, float* dbeta, float* dx,
+                                         void* stream) {
+  return backward(x, dy, n, c, mean, invstd, scale, shift, workspace, dgamma, dbeta, dx, stream, NARROW_C);
+}
+
+// The same functions up to CG_DENSE_MAX_C channels (catgrasp_amd_dense.h): the widths of PointNetSeg's per-point head.
+extern "C" long cg_bn_wide_workspace(long n, int c) { return workspace_size(n, c, CG_DENSE_MAX_C); }
+
+extern "C" int cg_bn_relu_train_forward_wide(const float* x, long n, int c, const float* gamma, const float* beta, float eps, float* workspace,
+                                             float* mean, float* var, float* invstd, float* scale, float* shift, float* y, void* stream) {
+  return forward(x, n, c, gamma, beta, eps, workspace, mean, var, invstd, scale, shift, y, stream, CG_DENSE_MAX_C);
+}
+
+extern "C" int cg_bn_relu_train_backward_wide(const float* x, const float* dy, long n, int c, const float* mean, const float* invstd,
+                                              const float* scale, const float* shift, float* workspace, float* dgamma, float* dbeta, float* dx,
+                                              void* stream) {
+  return backward(x, dy, n, c, mean, invstd, scale, shift, workspace, dgamma, dbeta, dx, stream, CG_DENSE_MAX_C);
 }
