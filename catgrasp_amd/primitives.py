@@ -96,28 +96,44 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     return out
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, start=None):
-    """pointnet2.py:101-129: FPS -> gather centroids -> ball query -> grouped, centred xyz ++ point features."""
-    require_cuda(xyz)
-    xyz = _f32(xyz)
-    B, N, C = xyz.shape
-    S = npoint
-    fps_idx, new_xyz = farthest_point_sample(xyz, npoint, start, return_xyz=True)      # new_xyz = index_points(xyz, fps_idx)
-    idx = query_ball_point(radius, nsample, xyz, new_xyz)
-    K = idx.shape[2]
+def group_points(xyz, points, new_xyz, idx, return_grouped_xyz=False, what='group_points'):
+    """The tail of sample_and_group on explicit neighbour lists (pointnet2.py:118-123): xyz (B,N,3), points (B,N,D) | None, new_xyz
+    (B,S,3), idx (B,S,K) int64 -> new_points (B,S,K,3+D) = cat(xyz[idx] - new_xyz, points[idx]); return_grouped_xyz=True: also
+    grouped_xyz (B,S,K,3) = xyz[idx], written by the same launch.  An index outside [0, N) -- the empty ball's sentinel N among them --
+    raises IndexError (`what` names the caller in its message)."""
+    require_cuda(xyz, points, new_xyz, idx)
+    xyz = _f32(xyz); new_xyz = _f32(new_xyz)
+    idx = idx.contiguous().long()
+    B, N, _ = xyz.shape
+    S, K = idx.shape[1], idx.shape[2]
+    if idx.shape[0] != B or tuple(new_xyz.shape) != (B, S, 3):
+        raise ValueError(f'group_points: xyz {tuple(xyz.shape)}, new_xyz {tuple(new_xyz.shape)} and idx {tuple(idx.shape)} do not match')
     D = 0
     if points is not None:
         points = _f32(points)
         D = points.shape[2]
     new_points = torch.empty((B, S, K, 3 + D), dtype=torch.float32, device=xyz.device)
-    grouped_xyz = torch.empty((B, S, K, 3), dtype=torch.float32, device=xyz.device) if returnfps else None
+    grouped_xyz = torch.empty((B, S, K, 3), dtype=torch.float32, device=xyz.device) if return_grouped_xyz else None
     err = torch.zeros((1,), dtype=torch.int32, device=xyz.device)
     check(L.lib().cg_group_points(_p(xyz), _p(points), _p(new_xyz), _p(idx), B, N, S, K, D,
                                   _p(new_points), _p(grouped_xyz), _p(err), _stream()), 'cg_group_points')
-    _raise_if(err, 'sample_and_group (a query ball was empty)')
+    _raise_if(err, what)
+    if return_grouped_xyz:
+        return new_points, grouped_xyz
+    return new_points
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, start=None):
+    """pointnet2.py:101-129: FPS -> gather centroids -> ball query -> grouped, centred xyz ++ point features."""
+    require_cuda(xyz)
+    xyz = _f32(xyz)
+    fps_idx, new_xyz = farthest_point_sample(xyz, npoint, start, return_xyz=True)      # new_xyz = index_points(xyz, fps_idx)
+    idx = query_ball_point(radius, nsample, xyz, new_xyz)
+    what = 'sample_and_group (a query ball was empty)'
     if returnfps:
+        new_points, grouped_xyz = group_points(xyz, points, new_xyz, idx, return_grouped_xyz=True, what=what)
         return new_xyz, new_points, grouped_xyz, fps_idx
-    return new_xyz, new_points
+    return new_xyz, group_points(xyz, points, new_xyz, idx, what=what)
 
 
 def sample_and_group_all(xyz, points):

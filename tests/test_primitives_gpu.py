@@ -1,7 +1,9 @@
 """GPU parity of the PointNet++ primitives (pointnet2.py:14-149) vs the CPU oracle restatement
 (oracle/pointnet_ref.py, itself checked against the imported reference in tests/golden).
 Index outputs are exact; ball-query membership may differ from the torch-CPU evaluation only for points
-whose expanded squared distance is within float rounding (1e-6 relative band) of r^2."""
+whose expanded squared distance is within float rounding (1e-6 relative band) of r^2.
+The exact cases -- dyadic inputs without a rounding band, planted balls at every kernel boundary, general clouds with an r^2 no pair is
+near, gathers as bit patterns -- are in tests/test_primitives_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
