@@ -22,8 +22,9 @@ batch-statistics mode with ReLU (forward and backward) a ninth, include/catgrasp
 screened form of the fused per-point pass a tenth, include/catgrasp_amd_screen.h, described by `screen_signatures()`, and the NUNOCS
 training loss (forward and backward) an eleventh, include/catgrasp_amd_loss.h, described by `loss_signatures()`.  The gradients of the
 dense per-row layers (weight, bias, input, per-group column sums) and BatchNorm + ReLU at the widths of PointNetSeg's head have a
-twelfth, which lives inside the package, catgrasp_amd/include/catgrasp_amd_dense.h, described by `dense_signatures()`.  `lib()` binds
-and requires all twelve.
+twelfth, which lives inside the package, catgrasp_amd/include/catgrasp_amd_dense.h, described by `dense_signatures()`, and the closed-form
+training of PointNet's conv + BatchNorm + max-pool layer a thirteenth, next to it, catgrasp_amd/include/catgrasp_amd_pool.h, described by
+`pool_signatures()`.  `lib()` binds and requires all thirteen.
 """
 import ctypes
 import os
@@ -45,6 +46,7 @@ BN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_bn.h')   # ba
 SCREEN_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_screen.h')   # the screened per-point pass: likewise
 LOSS_HEADER_PATH = os.path.join(_PKG, '..', 'include', 'catgrasp_amd_loss.h')   # the NUNOCS training loss: likewise
 DENSE_HEADER_PATH = os.path.join(_PKG, 'include', 'catgrasp_amd_dense.h')   # the dense layers' gradients: likewise, inside the package
+POOL_HEADER_PATH = os.path.join(_PKG, 'include', 'catgrasp_amd_pool.h')   # the pooled layer's closed-form training: likewise
 _lib = None
 
 _SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -156,6 +158,12 @@ def dense_signatures():
         return signatures(f.read())
 
 
+def pool_signatures():
+    """signatures() of catgrasp_amd/include/catgrasp_amd_pool.h: same parser, same type mapping."""
+    with open(POOL_HEADER_PATH) as f:
+        return signatures(f.read())
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -166,7 +174,7 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         sigs = {**signatures(), **cluster_signatures(), **sparse_signatures(), **pointgroup_signatures(), **scene_signatures(),
                 **neighbors_signatures(), **kdtree_signatures(), **sparse_grad_signatures(), **bn_signatures(), **screen_signatures(),
-                **loss_signatures(), **dense_signatures()}
+                **loss_signatures(), **dense_signatures(), **pool_signatures()}
         missing = [s for s in sorted(sigs) if not hasattr(l, s)]
         if missing:
             raise CatgraspAmdError(f'libcatgrasp_amd.so lacks symbols {missing}; rebuild it')

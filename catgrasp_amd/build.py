@@ -39,6 +39,7 @@ def build(force=False, verbose=True):
                                                                  'catgrasp_amd_scene.h', 'catgrasp_amd_neighbors.h', 'catgrasp_amd_kdtree.h', 'catgrasp_amd_sparse_grad.h', 'catgrasp_amd_bn.h',
                                                                  'catgrasp_amd_screen.h', 'catgrasp_amd_loss.h')]
     hdrs.append(os.path.join(PKG_DIR, 'include', 'catgrasp_amd_dense.h'))      # the dense layers' gradients: a header inside the package
+    hdrs.append(os.path.join(PKG_DIR, 'include', 'catgrasp_amd_pool.h'))       # the pooled layer's closed-form training: likewise
     objs = []
     jobs = []
     for s in srcs:

@@ -17,23 +17,34 @@ graph and double backward (the functions are once differentiable).  n_out must b
 
 USE_TORCH_OPS runs the head on torch ops over the same walk (the concatenation, Conv1d, BatchNorm1d, relu: the arithmetic of
 `pointnet2.PointNetSeg`'s training forward).  It is the baseline of scripts/pointnet_seg_train_time.py and of one
-equality-within-bar test; torch states no summation order for it."""
+equality-within-bar test; torch states no summation order for it.
+
+ENCODER_ON_HIP (opt-in, False by default: the default training forward keeps its bits) walks the encoder on HIP as well
+(pool_autograd.encoder_train): the 64- and 128-wide per-point layers through dense_autograd.linear + bn_relu_train (the 6 -> 64 layers
+on rows and weights zero-padded to 8 columns), the three conv + BatchNorm + max-pool layers (stn.conv3, fstn.conv3 with ReLU, conv3
+without) through pool_autograd.conv_bn_max_train, whose closed form stores no (B N, 1024) tensor forward or backward.  What stays on
+torch ops with the switch set: the two bmm's and the FC tails of the two transform nets on B rows.  USE_TORCH_OPS keeps precedence;
+eval mode is untouched."""
 import torch
 import torch.nn.functional as F
 
 from . import pointnet2
 from .dense_autograd import seg_head_train
+from .pool_autograd import encoder_train
 
 USE_TORCH_OPS = False
+ENCODER_ON_HIP = False
 
 
 class PointNetSeg(pointnet2.PointNetSeg):
     """forward(x (B, N, D)) -> ((B, N, n_out), trans_feat (B, 64, 64))."""
 
     def _encode(self, x):
-        """The training-mode encoder on torch ops (PointNetEncoder._torch_forward without the concatenation):
-        -> (g (B, 1024), pointfeat (B, N, 64) point-major, trans_feat)."""
+        """The training-mode encoder on torch ops (PointNetEncoder._torch_forward without the concatenation), or, with ENCODER_ON_HIP,
+        pool_autograd.encoder_train: -> (g (B, 1024), pointfeat (B, N, 64) point-major, trans_feat)."""
         enc = self.feat
+        if ENCODER_ON_HIP and not USE_TORCH_OPS:
+            return encoder_train(enc, x)
         D = x.shape[2]
         trans = enc.stn._torch_forward(x.transpose(2, 1))
         xyz = torch.bmm(x[:, :, :3], trans)
