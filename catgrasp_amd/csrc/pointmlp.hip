@@ -341,117 +341,153 @@ __device__ __forceinline__ void pointmlp_max_body(Args a) {
       const bool in_range = w_ok && ctl[1] == 0;
       exact = first || !in_range;
       if (!exact) {
-        // ---- screen + select, three (then three, then two) of the wave's eight channel blocks at a time: their 3 x 2 accumulators are
-        // the 96 accumulation registers the exact stream uses, the A fragments (both row tiles) are the bf16 conversion of the f32 image (hi) and
-        // the hlo image (lo), read per 16-channel step ----
+        // ---- screen + select as a rolling pipeline over the wave's eight channel blocks: one block's products in flight (2 accumulators)
+        // beside the previous, finished block (2 accumulators), ping-ponged; the finished block's select is cut into eight slices, one
+        // behind each 16-channel step of the block in flight, so that its vector work runs between this wave's own MFMAs ----
         const float* ap = h2 + l31 * S128 + lhi * 8;
         const frag* lp = (const frag*)(hlo + l31 * S64 + lhi * 4);
         const float* hq = hn + lhi * 4;
+        // The wave's 64 steps (8 blocks x 8 sixteen-channel steps) are one linear weight stream: the pair of step s = 8 blk + kc lies at
+        // (2 s + h) * 64 fragments from bp.  Four rotating register pairs hold the steps s .. s + 3; a step's pair is requested for step
+        // s + 4 as soon as its six products are issued (24 MFMAs ahead).  No request leaves the wave's 64 steps: the last block is peeled.
+        const frag* bp = (const frag*)w3s_t + (size_t)(w * 8) * (8 * 2 * 64) + lane;       // [nb][kc][hi | lo][lane]
+        frag bq[4][2];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { bq[s][0] = bp[(2 * s) * 64]; bq[s][1] = bp[(2 * s + 1) * 64]; }
+        // A operands, both row tiles.  They are the same for every block, so the hi fragments of all eight steps (the bf16 conversion of
+        // the f32 image) are formed once per tile and stay in registers (64): read and converted per block they cost 384 instead of
+        // 144 ds_read_b128 per wave and tile, and the step more than the rolling select gained.  The lo fragments of the hlo image are
+        // requested behind a step's fourth product for the next step.
+        frag ahr[8][2], fl[2];
+#pragma unroll
+        for (int kc = 0; kc < 8; ++kc) {
+          const f32x4 f0 = *(const f32x4*)(ap + kc * 16), f1 = *(const f32x4*)(ap + kc * 16 + 4);
+          const f32x4 f2 = *(const f32x4*)(ap + 32 * S128 + kc * 16), f3 = *(const f32x4*)(ap + 32 * S128 + kc * 16 + 4);
+          ahr[kc][0] = scr_hi8(f0, f1); ahr[kc][1] = scr_hi8(f2, f3);
+        }
+        fl[0] = lp[0]; fl[1] = lp[32 * (S64 / 4)];
+        // ---- select: lane = channel, registers = 32 points.  T = max(exact running max, the tile's own lower bound) ----
+        // E = kw * hn + SCR_FLOOR.  Pass 1: lb = max(c - kw * hn) - SCR_FLOOR; pass 2: list c + kw * hn >= T - SCR_FLOOR.  Two elements
+        // per packed fma; the compare's bit is shifted into the lane's mask through the carry (m = 2 m + bit), top register first.
+        // Eight slices: the four quarters of pass 1 (T behind the fourth), then the four quarters of pass 2 from the top.  A slice is cut
+        // again into four parts of one packed fma each: (row tile 0 | 1) x (register pair), in the order the masks fill.
+        float wnn = 0.f, kw = 0.f, lb = -INFINITY, T = 0.f;     // wnn: the row-norm bound of the block in flight, requested a phase ahead
+        unsigned m0 = 0, m1 = 0;
+        f32x4 nn0 = *(const f32x4*)hq, nn1 = *(const f32x4*)(hq + 32);      // the next slice's hn, requested a step ahead
+        auto part = [&](const f32x16* fin, int sl, int pt, f32x4 n0, f32x4 n1) __attribute__((always_inline)) {
+          const int rt = pt >> 1;
+          const f32x4 n = rt ? n1 : n0;
+          if (sl < 4) {
+            const int q = sl, j = (pt & 1) * 2;
+            const f32x2 nkw = {-kw, -kw};
+            const f32x2 t = __builtin_elementwise_fma(nkw, f32x2{n[j], n[j + 1]}, f32x2{fin[rt][q * 4 + j], fin[rt][q * 4 + j + 1]});
+            lb = fmaxf(fmaxf(sl == 0 && pt == 0 ? -INFINITY : lb, t[0]), t[1]);
+          } else {
+            const int q = 7 - sl, j = 2 - (pt & 1) * 2;
+            const f32x2 pkw = {kw, kw};
+            const f32x2 u = __builtin_elementwise_fma(pkw, f32x2{n[j], n[j + 1]}, f32x2{fin[rt][q * 4 + j], fin[rt][q * 4 + j + 1]});
+            if (rt == 0)
+              asm("v_cmp_ge_f32 vcc, %1, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+                  "v_cmp_ge_f32 vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m0) : "v"(u[1]), "v"(u[0]), "v"(T) : "vcc");
+            else
+              asm("v_cmp_ge_f32 vcc, %1, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
+                  "v_cmp_ge_f32 vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m1) : "v"(u[1]), "v"(u[0]), "v"(T) : "vcc");
+          }
+        };
+        // One 16-channel step of the block in flight (prod) with one slice of the finished block's select (sel), in issue order: every
+        // product is followed by its share of the requests and of the slice, and the order is pinned product by product -- left to
+        // itself the scheduler issues the six products first and the slice behind them, which is the serial form again.
+        // Per accumulator element the three products of a step stay in the order hi-lo, lo-hi, hi-hi, kc ascending from zero.
+        auto step = [&](f32x16* c, const f32x16* fin, const frag* bpb, int kc, int ch, bool prod, bool sel, bool last) __attribute__((always_inline)) {
+          const frag ah0 = ahr[kc][0], ah1 = ahr[kc][1], al0 = fl[0], al1 = fl[1];
+          const frag bh = bq[kc & 3][0], bl = bq[kc & 3][1];
+          const bool next = prod && (!last || kc < 7);
+          const int kn = (kc + 1) & 7;
+          f32x4 n0 = {0}, n1 = {0};
+          float rm = 0.f;
+          if (prod) c[0] = mfma_x<false>(ah0, bl, c[0]);
+          if (sel) {
+            const int sn = (kc + 1) & 7, qn = sn < 4 ? sn : 7 - sn;      // quarter of the next slice (it wraps to the next block's first)
+            n0 = nn0; n1 = nn1;
+            nn0 = *(const f32x4*)(hq + qn * 8); nn1 = *(const f32x4*)(hq + 32 + qn * 8);
+            if (kc == 3) rm = rmax[ch];
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (prod) c[1] = mfma_x<false>(ah1, bl, c[1]);
+          __builtin_amdgcn_sched_barrier(0);
+          if (prod) c[0] = mfma_x<false>(al0, bh, c[0]);
+          if (sel) part(fin, kc, 0, n0, n1);
+          __builtin_amdgcn_sched_barrier(0);
+          if (prod) c[1] = mfma_x<false>(al1, bh, c[1]);
+          if (sel) part(fin, kc, 1, n0, n1);
+          if (next) { fl[0] = lp[kn * 2]; fl[1] = lp[32 * (S64 / 4) + kn * 2]; }
+          __builtin_amdgcn_sched_barrier(0);
+          if (prod) c[0] = mfma_x<false>(ah0, bh, c[0]);
+          if (sel) part(fin, kc, 2, n0, n1);
+          __builtin_amdgcn_sched_barrier(0);
+          if (prod) c[1] = mfma_x<false>(ah1, bh, c[1]);
+          if (prod && (!last || kc < 4)) {
+            bq[kc & 3][0] = bpb[(2 * (kc + 4)) * 64];
+            bq[kc & 3][1] = bpb[(2 * (kc + 4) + 1) * 64];
+          }
+          if (sel) part(fin, kc, 3, n0, n1);
+          if (sel && kc == 3) {
+            lb = fmaxf(lb - SCR_FLOOR, rm);
+            T = fmaxf(lb, __shfl_xor(lb, 32)) - SCR_FLOOR;
+            m0 = 0; m1 = 0;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        };
+        // the finished block's pairs join the tile's list (plain code behind the block's last slice: its accumulators are intact)
+        auto append = [&](const f32x16* fin, int ch) __attribute__((always_inline)) {
+          const int cnt = __popc(m0) + __popc(m1);
+          if (cnt) {
+            const int at0 = atomicAdd(&ctl[0], cnt);
+            int at = at0;
+            unsigned m = m0;
 #pragma unroll 1
-        for (int g = 0; g < 3; ++g) {
-          const int nb0 = w * 8 + g * 3;
-          const int nblk = g < 2 ? 3 : 2;
-          const frag* bp = (const frag*)w3s_t + (size_t)nb0 * (8 * 2 * 64) + lane;         // [nb][kc][hi | lo][lane]
-          f32x16 c[3][2];
+            for (int rt = 0; rt < 2; ++rt, m = m1) {
+              while (m) {
+                const int r = __ffs(m) - 1;
+                m &= m - 1;
+                if (at < SCR_CAP) list[at] = (unsigned short)(((rt * 32 + acc_row(r, lane)) << 10) | ch);
+                ++at;
+              }
+            }
+            if (a.stats) {               // the same slots, by static register index
 #pragma unroll
-          for (int p = 0; p < 3; ++p) { c[p][0] = f32x16{0}; c[p][1] = f32x16{0}; }
-          // weight fragments [p][hi | lo]: a block's pair for the next 16-channel step is requested into the same registers as soon as
-          // its six products of this step are issued, i.e. two blocks' products (12 MFMAs) ahead of its use
-          frag bq[6];
-#pragma unroll
-          for (int i = 0; i < 6; ++i) if ((i >> 1) < nblk) bq[i] = bp[((i >> 1) * 16 + (i & 1)) * 64];
-          // A operands of a 16-channel step, both row tiles: the f32 fragments (hi = their bf16 conversion) and the lo fragments of the
-          // hlo image, requested behind the previous step's products.  (Requested a whole step earlier they gained 0.1 %: not kept.)
-          f32x4 fa[4];
-          frag fl[2];
-          auto read_a = [&](int kc) {
-            fa[0] = *(const f32x4*)(ap + kc * 16); fa[1] = *(const f32x4*)(ap + kc * 16 + 4);
-            fa[2] = *(const f32x4*)(ap + 32 * S128 + kc * 16); fa[3] = *(const f32x4*)(ap + 32 * S128 + kc * 16 + 4);
-            fl[0] = lp[kc * 2]; fl[1] = lp[32 * (S64 / 4) + kc * 2];
-          };
-          read_a(0);
+              for (int r = 0; r < 16; ++r) {
+                const int i0 = at0 + __popc(m0 & ((1u << r) - 1)), i1 = at0 + __popc(m0) + __popc(m1 & ((1u << r) - 1));
+                if (((m0 >> r) & 1) && i0 < SCR_CAP) zt[i0] = fin[0][r];
+                if (((m1 >> r) & 1) && i1 < SCR_CAP) zt[i1] = fin[1][r];
+              }
+            }
+          }
+        };
+        // one phase: the eight steps of block `pblk` into `cur` (prod), each followed by one slice of block `sblk`'s select on `fin` (sel)
+        auto phase = [&](f32x16* cur, f32x16* fin, int pblk, int sblk, bool prod, bool sel, bool last) __attribute__((always_inline)) {
+          const frag* bpb = bp + pblk * (16 * 64);
+          const int ch = (w * 8 + sblk) * 32 + l31;
+          if (sel) kw = SCR_KAPPA * wnn;
+          if (prod) {
+            wnn = wn_t[(w * 8 + pblk) * 32 + l31];
+            cur[0] = f32x16{0}; cur[1] = f32x16{0};
+          }
 #pragma unroll
           for (int kc = 0; kc < 8; ++kc) {
-            const frag ah0 = scr_hi8(fa[0], fa[1]), ah1 = scr_hi8(fa[2], fa[3]), al0 = fl[0], al1 = fl[1];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-              if (p >= nblk) break;
-              const frag bh = bq[p * 2], bl = bq[p * 2 + 1];
-              c[p][0] = mfma_x<false>(ah0, bl, c[p][0]); c[p][1] = mfma_x<false>(ah1, bl, c[p][1]);
-              c[p][0] = mfma_x<false>(al0, bh, c[p][0]); c[p][1] = mfma_x<false>(al1, bh, c[p][1]);
-              c[p][0] = mfma_x<false>(ah0, bh, c[p][0]); c[p][1] = mfma_x<false>(ah1, bh, c[p][1]);
-              if (kc < 7) {
-                bq[p * 2] = bp[(p * 16 + (kc + 1) * 2) * 64];
-                bq[p * 2 + 1] = bp[(p * 16 + (kc + 1) * 2 + 1) * 64];
-              }
-              __builtin_amdgcn_sched_barrier(0);     // keep the requests here: the scheduler would sink them to their use
-            }
-            if (kc < 7) read_a(kc + 1);
+            step(cur, fin, bpb, kc, ch, prod, sel, last);
           }
-          // ---- select: lane = channel, registers = 32 points.  T = max(exact running max, the tile's own lower bound) ----
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            if (p >= nblk) break;
-            __builtin_amdgcn_sched_barrier(0);       // one block's select at a time: interleaved they need the registers of all three
-            const f32x16 c0 = c[p][0], c1 = c[p][1];
-            const int ch = (nb0 + p) * 32 + l31;
-            // E = kw * hn + SCR_FLOOR.  Pass 1: lb = max(c - kw * hn) - SCR_FLOOR; pass 2: list c + kw * hn >= T - SCR_FLOOR.  Two elements
-            // per packed fma; the compare's bit is shifted into the lane's mask through the carry (m = 2 m + bit), top register first.
-            const float kw = SCR_KAPPA * wn_t[ch];
-            const f32x2 pkw = {kw, kw}, nkw = {-kw, -kw};
-            float lb = -INFINITY;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const f32x4 n0 = *(const f32x4*)(hq + q * 8), n1 = *(const f32x4*)(hq + 32 + q * 8);
-#pragma unroll
-              for (int j = 0; j < 4; j += 2) {
-                const f32x2 t0 = __builtin_elementwise_fma(nkw, f32x2{n0[j], n0[j + 1]}, f32x2{c0[q * 4 + j], c0[q * 4 + j + 1]});
-                const f32x2 t1 = __builtin_elementwise_fma(nkw, f32x2{n1[j], n1[j + 1]}, f32x2{c1[q * 4 + j], c1[q * 4 + j + 1]});
-                lb = fmaxf(fmaxf(lb, t0[0]), t0[1]);
-                lb = fmaxf(fmaxf(lb, t1[0]), t1[1]);
-              }
-            }
-            lb = fmaxf(lb - SCR_FLOOR, rmax[ch]);
-            const float T = fmaxf(lb, __shfl_xor(lb, 32)) - SCR_FLOOR;
-            unsigned m0 = 0, m1 = 0;
-#pragma unroll
-            for (int q = 3; q >= 0; --q) {
-              const f32x4 n0 = *(const f32x4*)(hq + q * 8), n1 = *(const f32x4*)(hq + 32 + q * 8);
-#pragma unroll
-              for (int j = 2; j >= 0; j -= 2) {
-                const f32x2 u0 = __builtin_elementwise_fma(pkw, f32x2{n0[j], n0[j + 1]}, f32x2{c0[q * 4 + j], c0[q * 4 + j + 1]});
-                const f32x2 u1 = __builtin_elementwise_fma(pkw, f32x2{n1[j], n1[j + 1]}, f32x2{c1[q * 4 + j], c1[q * 4 + j + 1]});
-                asm("v_cmp_ge_f32 vcc, %1, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
-                    "v_cmp_ge_f32 vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m0) : "v"(u0[1]), "v"(u0[0]), "v"(T) : "vcc");
-                asm("v_cmp_ge_f32 vcc, %1, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc\n\t"
-                    "v_cmp_ge_f32 vcc, %2, %3\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m1) : "v"(u1[1]), "v"(u1[0]), "v"(T) : "vcc");
-              }
-            }
-            const int cnt = __popc(m0) + __popc(m1);
-            if (cnt) {
-              const int at0 = atomicAdd(&ctl[0], cnt);
-              int at = at0;
-              unsigned m = m0;
+          if (sel) append(fin, ch);
+        };
+        f32x16 ca[2], cb[2];
+        phase(ca, cb, 0, 0, true, false, false);               // fill
 #pragma unroll 1
-              for (int rt = 0; rt < 2; ++rt, m = m1) {
-                while (m) {
-                  const int r = __ffs(m) - 1;
-                  m &= m - 1;
-                  if (at < SCR_CAP) list[at] = (unsigned short)(((rt * 32 + acc_row(r, lane)) << 10) | ch);
-                  ++at;
-                }
-              }
-              if (a.stats) {               // the same slots, by static register index
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                  const int i0 = at0 + __popc(m0 & ((1u << r) - 1)), i1 = at0 + __popc(m0) + __popc(m1 & ((1u << r) - 1));
-                  if (((m0 >> r) & 1) && i0 < SCR_CAP) zt[i0] = c0[r];
-                  if (((m1 >> r) & 1) && i1 < SCR_CAP) zt[i1] = c1[r];
-                }
-              }
-            }
-          }
+        for (int i = 0; i < 3; ++i) {
+          phase(cb, ca, 2 * i + 1, 2 * i, true, true, false);
+          phase(ca, cb, 2 * i + 2, 2 * i + 1, true, true, false);
         }
+        phase(cb, ca, 7, 6, true, true, true);
+        phase(ca, cb, 7, 7, false, true, true);                // drain
         __syncthreads();
         const int n = ctl[0];
         if (n > SCR_CAP) {
